@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — ns/day (and Matom-steps/s) of the MI355X nonbonded engine on BASELINE.json's workloads.
 
-    python bench.py --gpus N --steps K --warmup W [--workload lj1m|lj256k|6mrr_pme|6mrr_direct|6mrr_rf64|6mrr_rf32|argon4096|memlimit]
+    python bench.py --gpus N --steps K --warmup W [--workload lj1m|lj256k|6mrr_pme|6mrr_direct|6mrr_rf64|6mrr_rf32|argon4096|memlimit] [--dump-outputs DIR]
 
 One "step" = one velocity-Verlet MD step (forces + integration + amortised neighbour-list upkeep) of the whole
 system, state resident in HBM.  N = 1: the whole box on one GPU.  N > 1 (launched by torch.distributed.run,
@@ -100,11 +100,35 @@ def make_case(workload):
     raise SystemExit(f"unknown workload {workload}")
 
 
+_native_oracle_dir = None
+
+
+def native_oracle():
+    """oracle.pyoracle with its -O3 -march=native library (oracle/Makefile `native`) built for this host in a scratch directory: the
+    benchmark writes nothing into the source tree, which may be read-only where it runs.  Built once per process."""
+    global _native_oracle_dir
+    from oracle import pyoracle as orc
+    if _native_oracle_dir is None:
+        import atexit
+        import shutil
+        import tempfile
+        d = tempfile.mkdtemp(prefix="mhip_oracle_")
+        atexit.register(shutil.rmtree, d, True)
+        os.mkdir(os.path.join(d, "oracle"))
+        for f in os.listdir(os.path.join(ROOT, "oracle")):          # the Makefile and the sources, under the layout it expects (../include)
+            if f == "Makefile" or f.endswith((".cpp", ".h")):
+                os.symlink(os.path.join(ROOT, "oracle", f), os.path.join(d, "oracle", f))
+        os.symlink(os.path.join(ROOT, "include"), os.path.join(d, "include"))
+        orc._HERE = os.path.join(d, "oracle")                         # where pyoracle builds and loads its libraries
+        orc.build(native=True)
+        _native_oracle_dir = d
+    return orc
+
+
 def cpu_baseline(case, dtype, dt, budget_s=20.0):
     """The Molly-algorithm CPU restatement (oracle, kind "port") timed on this host's cores on a bounded
     sample of the same workload: same atoms, same parameters, a handful of steps."""
-    from oracle import pyoracle as orc
-    orc.build(native=True)
+    orc = native_oracle()
     host = host_info()
     nthreads = max(1, host["usable_cores"])      # every core this process may run on (round 5 capped the leg at 64 threads)
     o = orc.from_case(case, dtype)
@@ -219,9 +243,9 @@ def measure_traffic(workload, timeout_s=90):
     return out or None
 
 
-def run_single(m, workload, args, steps, warmup, profile_steps):
-    """One workload on one GPU → (record, case, dtype, dt).  Timed region: exactly `steps` steps per window, inputs resident in HBM,
-    stream drained on both sides."""
+def run_single(m, workload, args, steps, warmup, profile_steps, outputs=None):
+    """One workload on one GPU → (record, case, dtype, dt).  Timed region: exactly `steps` steps, inputs resident in HBM,
+    stream drained on both sides.  outputs (a dict): receives the state the last timed step left, as a caller reads it back."""
     L = m.lib()
     case, dtype, dt = make_case(workload)
     s = case.system(m, dtype)
@@ -243,18 +267,17 @@ def run_single(m, workload, args, steps, warmup, profile_steps):
     first = equil + warmup
     # The K timed steps are taken AS SCHEDULED — wherever searches and prunes of the pair lists happen to fall.  A window shorter than
     # the life of an outer pair list (≈ 100 steps at 1M atoms; a search costs ≈ 10 plain steps) measures 0.14 or 0.22 ms/step for the
-    # same code depending on whether a search falls into it, so short windows are repeated back to back until they cover at least
-    # 100 steps (one whole list cycle) and the headline is their mean; every window is K steps between two stream syncs.
-    n_win = 1 if steps >= 100 else -(-100 // steps)
-    win_ms = []
-    for _ in range(n_win):
-        s._check(L.mhip_synchronize(ctx))
-        t0 = time.perf_counter()
-        run(first, steps)                                        # timed: exactly K steps; returns after a stream sync
-        s._check(L.mhip_synchronize(ctx))
-        win_ms.append((time.perf_counter() - t0) * 1e3 / steps)
-        first += steps
-    ms_per_step = float(np.mean(win_ms))
+    # same code depending on whether a search falls into it: ask for K >= 100 for a figure that covers a whole list cycle.
+    s._check(L.mhip_synchronize(ctx))
+    t0 = time.perf_counter()
+    run(first, steps)                                            # timed: exactly K steps; returns after a stream sync
+    s._check(L.mhip_synchronize(ctx))
+    ms_per_step = (time.perf_counter() - t0) * 1e3 / steps
+    first += steps
+    if outputs is not None:      # (untimed) coordinates and velocities after the K-th timed step, read back as mhip_get_state hands them out
+        s.pull_state()
+        outputs[workload + "_coords"] = s.coords.copy()
+        outputs[workload + "_velocities"] = s.velocities.copy()
     # separate pass with hipEvent stage timers on the engine's stream (never mixed into the timed region).  It follows the timed steps
     # without a pause: a mhip_get_stats in between (an export-sized kernel + host work, tens of ms) left the GPU idle long enough for
     # its clocks to drop, and a 200-step pass measured every kernel 6 % slow (force pass 92.8 against 87.1 µs on one box).
@@ -264,13 +287,12 @@ def run_single(m, workload, args, steps, warmup, profile_steps):
     s._check(L.mhip_set_profiling(ctx, 0))
     s._check(L.mhip_check_finite(ctx))
     s.close()
-    extra = {"timed_window": "as scheduled" if n_win == 1 else f"as scheduled: mean of {n_win} consecutive windows of {steps} steps (one whole pair-list cycle)",
-             "window_ms_per_step": {"n": n_win, "mean": ms_per_step, "min": float(min(win_ms)), "max": float(max(win_ms))},
+    extra = {"timed_window": "as scheduled",
              "list_upkeep_in_profile_pass": {"outer_searches": st["prof_calls"][1], "prunes": st["prof_calls"][4], "steps": profile_steps}}   # launches counted by the stage timers
     return ms_per_step, st, extra, case, dtype, dt
 
 
-def run_force_calls(m, workload, args):
+def run_force_calls(m, workload, args, outputs=None):
     """The reference's own GPU benchmark shape (benchmark/benchmark_gpu_tiles.jl:103-165): the median wall time of one forces! call and of
     one potential_energy call — each drained — with a step counter that advances by one per call, so that every tenth call is a rebuild step
     of the GPU neighbour finder.  --steps = the samples (the reference: 10).  One record per case (dense, sparse)."""
@@ -296,6 +318,9 @@ def run_force_calls(m, workload, args):
             t0 = time.perf_counter(); forces(k); tf.append((time.perf_counter() - t0) * 1e3)
         for k in range(args.steps):
             t0 = time.perf_counter(); energy(k); te.append((time.perf_counter() - t0) * 1e3)
+        if outputs is not None:      # the forces of the last timed forces call and the energy of the last timed energy call
+            outputs[name + "_forces"] = f.cpu().numpy()
+            outputs[name + "_potential_energy"] = np.array([pe.value], dtype=np.float64)
         s._check(L.mhip_set_profiling(ctx, 1))
         for k in range(args.steps, args.steps + 50):
             forces(k)
@@ -308,8 +333,7 @@ def run_force_calls(m, workload, args):
                "roofline_frac": (st["force_pass_bytes"] / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if kern_ms > 0 else None,
                "rebuilds": st["n_rebuilds"], "block_atoms": st["block_atoms"], "j_split": st["j_split"]}
         if not args.no_cpu_baseline:      # the oracle's forces over its own list, all cores (the reference's forces! minus the neighbour search)
-            from oracle import pyoracle as orc
-            orc.build(native=True)
+            orc = native_oracle()
             o = orc.from_case(case, np.float32); o.native = True
             nt = min(os.cpu_count() or 1, 64)
             nl = o.neighbors("cell", nthreads=nt)
@@ -422,8 +446,7 @@ def memlimit_oracle_check(W, x, f, box, n_inner=100_000):
     """Forces of the ≈ 10⁵ atoms in a cube at the box centre against the fp64 oracle evaluated on that cube plus a shell of one cutoff around it (an isolated
     cluster in a box wide enough that no image interacts: every partner of an inner atom is in the cluster, so its force is the whole system's)."""
     import torch
-    from oracle import pyoracle as orc
-    orc.build(native=True)
+    orc = native_oracle()
     P = W.MEMLIMIT
     a = (n_inner * P["volume_per_atom"]) ** (1.0 / 3.0)
     if a + 2 * P["r_cut"] + 0.5 > box:
@@ -567,11 +590,27 @@ def make_record(workload, case, dtype, dt, ms_per_step, st, extra, world, args, 
     return line
 
 
+DUMP_MAX_BYTES = 60_000_000      # (the files stay under 64 MB with their headers)
+
+
+def dump_outputs(d, outputs):
+    """--dump-outputs: every array as d/<name>.npy.  Beyond DUMP_MAX_BYTES in all, every array keeps the same fraction of its rows,
+    chosen by a fixed seed (the same rows in every run of the same arguments)."""
+    os.makedirs(d, exist_ok=True)
+    total = sum(a.nbytes for a in outputs.values())
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if total > DUMP_MAX_BYTES and a.shape[0] > 1:
+            k = max(1, a.shape[0] * DUMP_MAX_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], k, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--warmup", type=int, default=500)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 2000; forces calls of argon4096: 100)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed warm-up steps before them (default 500; argon4096: 10)")
     ap.add_argument("--workload", default=os.environ.get("MOLLYHIP_BENCH_WORKLOAD", "lj1m"))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the 6mrr_pme and lj256k records that the default single-GPU run appends")
@@ -584,7 +623,18 @@ def main():
     ap.add_argument("--memlimit-start", type=int, default=1_000_000, help="--workload memlimit: first atom count (doubled until a size fails)")
     ap.add_argument("--memlimit-max", type=int, default=0, help="--workload memlimit: stop doubling beyond this atom count (0: until a size fails)")
     ap.add_argument("--equil", type=int, default=None, help="untimed equilibration steps before the warm-up (SURVEY §8(d): 2000 for the LJ fluids, which start from a jittered lattice; 0 for 6mrr, which starts from an equilibrated structure)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what their last step computed as DIR/<name>.npy (at most 64 MB in all)")
     args = ap.parse_args()
+    force_calls = args.workload in FORCE_CALL_WORKLOADS      # (the defaults are sized for MD steps; the reference takes 10 samples of a forces call)
+    if args.steps is None:
+        args.steps = 100 if force_calls else 2000
+    if args.warmup is None:
+        args.warmup = 10 if force_calls else 500
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.workload == "memlimit":
+        raise SystemExit("--dump-outputs: the memlimit workload searches for a size and has no single timed path to dump")
+    outputs = {} if args.dump_outputs else None
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -608,7 +658,7 @@ def main():
     if world > 1 or os.environ.get("MOLLYHIP_FORCE_DOMAIN"):   # the env hook drives the N = 1 box through the multi-GPU host loop (overhead checks)
         case, dtype, dt = make_case(args.workload)
         from molly_jl_amd import domain   # spatial decomposition + RCCL halo exchange
-        result = domain.bench_distributed(m, case, dtype, dt, args, rank, local_rank, world)
+        result = domain.bench_distributed(m, case, dtype, dt, args, rank, local_rank, world, outputs=outputs)
         if rank != 0:
             return
         ms_per_step, st, extra = result
@@ -617,14 +667,14 @@ def main():
         line = run_memlimit(m, args)
         os.write(json_fd, (json.dumps(line) + "\n").encode())
         return
-    elif args.workload in FORCE_CALL_WORKLOADS:
-        if args.steps > 500:
-            args.steps, args.warmup = 100, 10            # (the defaults are sized for MD steps; the reference takes 10 samples)
-        line = run_force_calls(m, args.workload, args)
+    elif force_calls:
+        line = run_force_calls(m, args.workload, args, outputs)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         os.write(json_fd, (json.dumps(line) + "\n").encode())
         return
     else:
-        ms_per_step, st, extra, case, dtype, dt = run_single(m, args.workload, args, args.steps, args.warmup, args.profile_steps)
+        ms_per_step, st, extra, case, dtype, dt = run_single(m, args.workload, args, args.steps, args.warmup, args.profile_steps, outputs)
         # the counters behind roofline.traffic, taken in THIS run (two PMC passes of the same command in child processes, ≈ 20 s each) unless switched off; a run that
         # is itself such a child, or a box without rocprofv3, reads the committed files and says so
         live = measure_traffic(args.workload) if args.traffic == "measure" and not args.block_atoms else None
@@ -666,6 +716,8 @@ def main():
         if r.get("cpu_baseline"):
             summ[nm + "_cpu_ns_day"] = round(r["cpu_baseline"]["value"], 3)
     line["summary"] = summ
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     os.write(json_fd, (json.dumps(line) + "\n").encode())
 
 

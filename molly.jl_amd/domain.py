@@ -767,7 +767,7 @@ def make_interactions(case, dtype):
     return it
 
 
-def bench_distributed(m, case, dtype, dt, args, rank, local_rank, world):
+def bench_distributed(m, case, dtype, dt, args, rank, local_rank, world, outputs=None):
     """bench.py body for N > 1: strong scaling of one box over `world` GPUs.  Returns (ms_per_step, stats, extra) on rank 0."""
     if case.excluded is not None or case.bonds is not None:
         raise SystemExit("the multi-GPU path covers exception-free systems (LJ fluids); 6mrr runs as replicas only (SURVEY §8(e))")
@@ -838,21 +838,19 @@ def bench_distributed(m, case, dtype, dt, args, rank, local_rank, world):
             raise SystemExit(f"every form of the multi-GPU step loop failed (last on this rank: {why[:300] or 'a peer failed'})")
     loop_form = form
     first = equil + args.warmup
-    # the K timed steps are taken as scheduled; windows shorter than a pair-list cycle are repeated back to back until they cover
-    # 100 steps and the headline is their mean (bench.py's single-domain leg does the same)
-    n_win = 1 if args.steps >= 100 else -(-100 // args.steps)
-    win = []
-    for _ in range(n_win):
-        torch.cuda.synchronize(); dist.barrier()
-        t0 = time.perf_counter()
-        run.run(first, args.steps, dt)
-        torch.cuda.synchronize(); dist.barrier()
-        el = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
-        dist.all_reduce(el, op=dist.ReduceOp.MAX)
-        win.append(float(el.item()) * 1e3 / args.steps)
-        first += args.steps
-    ms_per_step = float(np.mean(win))
-    window = "as scheduled" if n_win == 1 else f"as scheduled: mean of {n_win} consecutive windows of {args.steps} steps (one whole pair-list cycle)"
+    # the K timed steps are taken as scheduled (bench.py's single-domain leg does the same)
+    torch.cuda.synchronize(); dist.barrier()
+    t0 = time.perf_counter()
+    run.run(first, args.steps, dt)
+    torch.cuda.synchronize(); dist.barrier()
+    el = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
+    dist.all_reduce(el, op=dist.ReduceOp.MAX)
+    ms_per_step = float(el.item()) * 1e3 / args.steps
+    first += args.steps
+    window = "as scheduled"
+    if outputs is not None:      # (untimed, collective) the whole box's coordinates and velocities after the K-th timed step, on rank 0
+        xs, vs = run.gather_global(case.n)
+        outputs[args.workload + "_coords"], outputs[args.workload + "_velocities"] = xs.astype(dtype), vs.astype(dtype)
     eng.set_profiling(True)
     run.run(first, args.profile_steps, dt)
     torch.cuda.synchronize()
@@ -875,6 +873,5 @@ def bench_distributed(m, case, dtype, dt, args, rank, local_rank, world):
     extra = {"parallelism": f"spatial bricks {grid[0]}x{grid[1]}x{grid[2]}, full-shell ghost coordinates via {transport}, "
                             f"{int(agg[3] / world)} ghosts / {int(agg[4] / world)} owned atoms per GPU, ghost margin {gm:.2f} nm "
                             f"({run.stats['plans']} ghost plans, {run.stats['prunes']} prunes in {run.stats['plan_checks']} checks)",
-             "per_gpu_force_pass_bytes": st["force_pass_bytes"], "ghost_fraction": agg[3] / max(agg[4], 1), "timed_window": window,
-             "window_ms_per_step": {"n": n_win, "mean": ms_per_step, "min": float(min(win)), "max": float(max(win))}}
+             "per_gpu_force_pass_bytes": st["force_pass_bytes"], "ghost_fraction": agg[3] / max(agg[4], 1), "timed_window": window}
     return ms_per_step, st, extra

@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -36,14 +37,25 @@ def _check_contract(d, n_gpus, steps, warmup):
     assert "workload" in d["config"] and "timed_window" in d["config"]
 
 
-def test_bench_single_gpu_record():
-    d = _record([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--workload", "lj256k", "--equil", "300", "--no-cpu-baseline", "--traffic", "file"])
+def test_bench_single_gpu_record(pkg, tmp_path):
+    """--steps K times exactly K steps, and --dump-outputs writes the state the last of them left"""
+    cmd = lambda steps, out: [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "5", "--workload", "lj256k", "--equil", "300", "--no-cpu-baseline",
+                              "--traffic", "file", "--dump-outputs", str(tmp_path / out)]
+    d = _record(cmd(20, "a"))
     _check_contract(d, 1, 20, 5)
     assert d["config"]["parallelism"] == "single domain"
-    assert d["config"]["timed_window"].startswith("as scheduled: mean of 5 consecutive windows of 20 steps")   # never placed
-    w = d["window_ms_per_step"]
-    assert w["n"] == 5 and w["min"] <= d["ms_per_step"] <= w["max"] and abs(w["mean"] - d["ms_per_step"]) < 1e-12
+    assert d["config"]["timed_window"] == "as scheduled" and "window_ms_per_step" not in d      # one window of exactly --steps steps, never placed (DESIGN §7)
     assert "secondary" not in d                                        # only the default workload appends the other configurations
+    assert sorted(os.listdir(tmp_path / "a")) == ["lj256k_coords.npy", "lj256k_velocities.npy"]
+    x, v = np.load(tmp_path / "a" / "lj256k_coords.npy"), np.load(tmp_path / "a" / "lj256k_velocities.npy")
+    assert x.shape == v.shape == (64 ** 3, 3) and x.dtype == v.dtype == np.float32 and np.isfinite(x).all() and np.isfinite(v).all()
+    # the state after 300 + 5 + 20 steps, not the initial one
+    import importlib
+    case = importlib.import_module("molly_jl_amd.workloads").lj_fluid(64, seed=2, dtype=np.float32)
+    assert np.abs(v - case.velocities).max() > 1e-3
+    # the steps asked for: 5 more timed steps end elsewhere
+    d25 = _record(cmd(25, "b"))
+    assert d25["steps"] == 25 and not np.array_equal(np.load(tmp_path / "b" / "lj256k_coords.npy"), x)
 
 
 def test_bench_default_workload_carries_the_other_configurations():
@@ -69,14 +81,18 @@ def test_bench_default_workload_carries_the_other_configurations():
     assert d["secondary"][1]["roofline"]["traffic_source"].startswith("profiles/") and d["lib_build_id"] and d["kernel_src_id"]
 
 
-def test_bench_two_ranks_record():
+def test_bench_two_ranks_record(tmp_path):
     port = _free_port()
     d = _record([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                 "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5", "--workload", "lj256k", "--equil", "300"],
+                 "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5", "--workload", "lj256k", "--equil", "300", "--dump-outputs", str(tmp_path)],
                 env={"MOLLYHIP_DIST_BACKEND": "gloo", "MOLLYHIP_FORCE_DEVICE": "0"})
     _check_contract(d, 2, 20, 5)
-    assert "spatial bricks 2x1x1" in d["config"]["parallelism"]
+    assert "spatial bricks 2x1x1" in d["config"]["parallelism"] and d["config"]["timed_window"] == "as scheduled"
     assert "cpu_baseline" not in d                                     # rank 0 at N = 1 only
+    # the whole box, gathered on rank 0 after the last timed step
+    x, v = np.load(tmp_path / "lj256k_coords.npy"), np.load(tmp_path / "lj256k_velocities.npy")
+    assert sorted(os.listdir(tmp_path)) == ["lj256k_coords.npy", "lj256k_velocities.npy"]
+    assert x.shape == v.shape == (64 ** 3, 3) and x.dtype == v.dtype == np.float32 and np.isfinite(x).all() and np.abs(v).max() > 0
 
 
 def test_bench_two_ranks_falls_back_collectively_when_a_form_of_the_step_loop_fails():
