@@ -210,7 +210,7 @@ template <class T> class Engine final : public EngineBase {
     double skin_in = 0, rc_max_ = 0; T r_prune2 = 0;
     // ghosted sub-domain whose ghost shell reaches r_list + ghost_margin: the ghost PLAN then lives as long as an outer list
     // (until some atom moved ghost_margin/2), so the dual list works here too and the host re-plans only when mhip_plan_disp2_dev says so
-    double ghost_margin = 0; const double* cm_ext = nullptr;
+    double ghost_margin = 0;
     int tri_mode = 0; double tri_bv[9] = {};   // TriclinicBoundary: 0 off, 1 approx_images, 2 exact images; basis vectors row-major
     bool tri_grid = false;                     // … with a cell grid in height-scaled fractional coordinates (else: one cell, every block sees every atom)
     long long grid_key = -1;
@@ -224,7 +224,19 @@ template <class T> class Engine final : public EngineBase {
     int64_t total_rows = 0, outer_rows = 0;      // rows (of four entries per lane, per wave) of the list the plain passes walk | of the outer list as searched
     // reductions
     DBuf<double> red_part, red_out, cm_step; double* h_red = nullptr; DBuf<T> vcm;
-    int n_cm_step = 0;   // cm_pending == 2: v_cm still lives as the per-block partials of the last k_vv2 (cm_step[0..4*n_cm_step))
+    // the Σ m v removal deferred to the next consumer of the velocities: none, subtract vcm, or re-sum n per-block partials {ΣPx, ΣPy, ΣPz, ΣM} at an address
+    class PendingCm {
+        int mode_ = 0; const double* parts_ = nullptr;
+      public:
+        int n = 0;   // the partials' count (outlives the removal: the halo paths read the last step's)
+        void none() { mode_ = 0; parts_ = nullptr; }
+        void subtract() { mode_ = 1; parts_ = nullptr; }
+        void resum(const double* p, int count) { mode_ = 2; parts_ = p; n = count; }
+        void moved(const double* p, int count) { parts_ = p; n = count; }   // the same sum, now at p (summed down by a pass in between)
+        int mode() const { return mode_; }
+        const T* vcm_arg(const T* vcm) const { return mode_ == 1 ? vcm : nullptr; }   // the kernel arguments: null when not pending that way
+        const double* parts_arg() const { return mode_ == 2 ? parts_ : nullptr; }
+    } pending_cm;
     // staging for host pointers
     DBuf<T> stage_a, stage_b; DBuf<int32_t> stage_i;
     // bonded
@@ -235,7 +247,7 @@ template <class T> class Engine final : public EngineBase {
     // (or fold_side_forces) adds it.  (Side streams, CU-masked streams and any-order launches for these chains all measured slower than one stream: DESIGN §4.)
     DBuf<T4> frc_side; const T4* pend_a = nullptr;
 
-    int cm_pending = 0; bool stale = true, minimg = false, params_set = false, state_set = false, frc_valid = false;
+    bool stale = true, minimg = false, params_set = false, state_set = false, frc_valid = false;
     bool coords_moved = false, export_needs_search = false; int64_t n_set_state_refresh = 0;
     int64_t last_build_step = std::numeric_limits<int64_t>::min();
     int64_t n_rebuilds = 0, n_force_calls = 0, n_gs_passes = 0; double last_rebuild_ms = 0;
@@ -357,7 +369,7 @@ template <class T> class Engine final : public EngineBase {
             if (ip.coul_kind != MHIP_COUL_NONE) rc_max = std::max(rc_max, ip.coul_rc);
             skin = G.no_list ? 0.0 : cfg.r_list - rc_max;
             rc_max_ = rc_max;
-            skin_in = ((n_ghost > 0 || host_prune) && !engine_sched) ? skin : std::min(skin, std::max(skin_in_adapted, std::max(1, env_int("MOLLYHIP_INNER_SKIN_PM", 100)) * 1e-3));   // (a skin the run has grown stays grown)
+            skin_in = ((n_ghost > 0 || host_prune) && !engine_sched) ? skin : std::min(skin, std::max(skin_in_adapted, inner_skin_floor()));   // (a skin the run has grown stays grown)
             const T rp = T(rc_max + skin_in);
             r_prune2 = (skin_in < skin) ? rp * rp : r_in2;
         }
@@ -441,6 +453,11 @@ template <class T> class Engine final : public EngineBase {
         BI = bi; JS = js;
         estimate_capacities();
     }
+    // a new launch shape (and cell grid): every list is void
+    void reblock() { choose_blocking(); stale = true; }
+    void regrid() { setup_grid(); reblock(); }
+    int rebuild_every() const { return cfg.rebuild_every > 0 ? cfg.rebuild_every : 10; }
+    static double inner_skin_floor() { return std::max(1, env_int("MOLLYHIP_INNER_SKIN_PM", 100)) * 1e-3; }   // (read at each use: a context may be made under another value)
 
     // ≙ set_cuda_launch_config! / reset_cuda_launch_config! (src/cuda_config.jl:17-47): the workgroup shape of the search and pair
     // kernels, block_atoms i-atoms × j_split waves per atom's list; (0, 0) returns to the automatic choice.  Lists are rebuilt.
@@ -453,7 +470,7 @@ template <class T> class Engine final : public EngineBase {
             user_bi = bi; user_js = js;
         }
         flush_cm();
-        choose_blocking(); stale = true;
+        reblock();
     }
 
     // ≙ optimize_cuda_launch_config! (ext/MollyCUDAExt.jl:594-642, src/cuda_config.jl:53-62): time a small candidate set on THIS system
@@ -478,7 +495,7 @@ template <class T> class Engine final : public EngineBase {
             float us = -1.f;
             try {
                 user_bi = c[0]; user_js = c[1];
-                choose_blocking(); stale = true; cur_dt = 0;
+                reblock(); cur_dt = 0;
                 ensure_built(step); pass_step = step;
                 launch_pair_kernel(false);                     // with a dual list: the pruning pass
                 if (prune_disp_exceeded) { after_forces(step); launch_pair_kernel(false); }
@@ -498,7 +515,7 @@ template <class T> class Engine final : public EngineBase {
         }
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
         user_bi = best_bi; user_js = best_js;                  // (0, 0 = automatic, when nothing could be timed)
-        choose_blocking(); stale = true; frc_valid = false;
+        reblock(); frc_valid = false;
         return n;
     }
 
@@ -527,12 +544,11 @@ template <class T> class Engine final : public EngineBase {
         if (bytes > 64 * 1024) MHIP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     }
 
-    const double* cm_src() const { return cm_ext ? cm_ext : (const double*)cm_step.p; }
     void flush_cm() {
-        if (!cm_pending) return;
+        if (!pending_cm.mode()) return;
         hipLaunchKernelGGL(k_shift_vel<T>, dim3(std::min(cdiv(n_owned, 256), 1024)), dim3(256), 0, stream, n_owned, vel[cur].p, (const T*)vcm.p,
-                           cm_pending == 2 ? cm_src() : (const double*)nullptr, n_cm_step);
-        cm_pending = 0; cm_ext = nullptr;
+                           pending_cm.parts_arg(), pending_cm.n);
+        pending_cm.none();
     }
 
     const T* to_device(const void* host_or_dev, size_t count, int mem_kind, DBuf<T>& stage) {
@@ -557,7 +573,7 @@ template <class T> class Engine final : public EngineBase {
             if (n_ghost > 0 || ghost_margin > 0 || host_prune) dual_disabled = true;
             else if (outer_margin > 0.06) ++margin_halvings; else if (!margin_zero) margin_zero = true; else dual_disabled = true;
             if (debug_on) std::fprintf(stderr, "[mhip] dual list %s (capacity): %s\n", dual_disabled ? "off" : (margin_zero ? "without outer margin" : "margin halved"), e.msg.c_str());
-            setup_grid(); choose_blocking(); stale = true;
+            regrid();
             rebuild(step_n);
         }
     }
@@ -662,7 +678,7 @@ template <class T> class Engine final : public EngineBase {
             inner_valid = false; inner_is_outer = false; prune_disp_exceeded = false; ghost_flags_in_ok = false;
             if (cur_dt > 0 && skin_in < skin && !host_prune) {   // inside a run: how fast is the fastest atom? (sizes the inner skin before the first prune)
                 (void)max_disp2_since(pos_snap);
-                adapt_inner_skin(drift_ahead(0.0, 1, cfg.rebuild_every > 0 ? cfg.rebuild_every : 10));
+                adapt_inner_skin(drift_ahead(0.0, 1, rebuild_every()));
             }
         }
         if (lazy_single) {
@@ -772,6 +788,14 @@ template <class T> class Engine final : public EngineBase {
     bool in_lang_fused = false;      // inside mhip_langevin_run of a small system whose last force launch integrates (the pair launch's extra workgroup then sums the Σ m v partials, as inside mhip_vv_run)
     bool in_lang_async = false;      // … and whose list checks are measured by that launch (no Andersen coupling behind it: the speeds the check reads would not be the run's)
     bool async_ok() const { return (in_vv_fused || in_lang_async) && dual && n_ghost == 0 && !host_prune && inner_valid && !stale; }
+    // the check of `step` from the n_parts per-block maxima in trk_part: reduce, copy, event
+    void issue_track(int n_parts, int64_t step) {
+        if (!h_trk) MHIP_HIP(hipHostMalloc((void**)&h_trk, 4 * sizeof(float)));
+        if (!ev_trk) MHIP_HIP(hipEventCreateWithFlags(&ev_trk, hipEventDisableTiming));
+        hipLaunchKernelGGL(k_track_reduce, dim3(1), dim3(256), 0, stream, n_parts, (const float*)trk_part.p, trk_out.p, h_trk);   // (straight into pinned host memory)
+        MHIP_HIP(hipEventRecord(ev_trk, stream));
+        trk_issued = true; trk_step = step; trk_prev_vmax = last_vmax; trk_prune_id = n_filters; trk_outer_id = n_outer;
+    }
     void resolve_track(int64_t step) {
         if (!trk_issued) return;
         MHIP_HIP(hipEventSynchronize(ev_trk));
@@ -780,7 +804,7 @@ template <class T> class Engine final : public EngineBase {
         prev_vmax = trk_prev_vmax; last_vmax = std::sqrt((double)h_trk[2]);   // (the speed of the check before, as it was when this one was issued: a run cut into chunks decides alike)
         ++n_disp_checks;
         if (!dual || stale || !inner_valid || n_ghost > 0 || n_filters != trk_prune_id || n_outer != trk_outer_id) return;   // the lists it measured have been replaced meanwhile
-        const int every = cfg.rebuild_every > 0 ? cfg.rebuild_every : 10;
+        const int every = rebuild_every();
         const int64_t so_far = trk_step - last_prune_step;
         const double ahead = drift_ahead(d, so_far, every);
         if (debug_on) std::fprintf(stderr, "[mhip] step %lld: measured at %lld: d %.5f d_outer %.5f v_max %.4f\n", (long long)step, (long long)trk_step, d, d_outer, last_vmax);
@@ -814,10 +838,10 @@ template <class T> class Engine final : public EngineBase {
     // rebuild step of the cadence (find_neighbors at step_n % n_steps == 0): a fresh search, or — with the dual list —
     // a filter pass, falling back to the search when it is due or an atom moved more than half the margin
     void refresh(int64_t step_n) {
-        const int every = cfg.rebuild_every > 0 ? cfg.rebuild_every : 10;
+        const int every = rebuild_every();
         if (want_margin_zero && !margin_zero && n_ghost == 0) {
             if (debug_on) std::fprintf(stderr, "[mhip] outer margin dropped (inner skin %.3f nm leaves it no second prune)\n", skin_in);
-            margin_zero = true; setup_grid(); choose_blocking(); stale = true;
+            margin_zero = true; regrid();
         }
         if (!dual && lazy_single && !stale && step_n > last_prune_step) {
             // single list built with r_list at step last_prune_step: it still holds every pair within the cutoffs unless somebody moved skin/2
@@ -862,10 +886,10 @@ template <class T> class Engine final : public EngineBase {
         if (!prune_disp_exceeded) return;
         prune_disp_exceeded = false;
         if (n_ghost > 0) throw ApiError{MHIP_ERR_STATE, "an atom moved more than half the ghost margin since the ghost plan: re-plan earlier (mhip_plan_disp2_dev)"};
-        const int every = cfg.rebuild_every > 0 ? cfg.rebuild_every : 10;
+        const int every = rebuild_every();
         // If that keeps happening before the outer list has paid for itself (fast light atoms, small time step), the dual list
         // is a loss: fall back to a fresh search at every rebuild step.
-        if (step_n - last_outer_step <= 2 * (int64_t)every) { if (++early_outer >= 3) { if (debug_on) std::fprintf(stderr, "[mhip] dual list off (outer list outrun 3x)\n"); dual_disabled = true; setup_grid(); choose_blocking(); stale = true; } }
+        if (step_n - last_outer_step <= 2 * (int64_t)every) { if (++early_outer >= 3) { if (debug_on) std::fprintf(stderr, "[mhip] dual list off (outer list outrun 3x)\n"); dual_disabled = true; regrid(); } }
         else early_outer = 0;
         rebuild(step_n);
     }
@@ -876,19 +900,17 @@ template <class T> class Engine final : public EngineBase {
     // continued in chunks then walks the same lists in the same order as the uncut run and reproduces it bit for bit.
     bool vel_check_due = false;   // velocities were replaced since the last validity check of the lists
     void start_lists(int64_t first_step) {
-        const int every = cfg.rebuild_every > 0 ? cfg.rebuild_every : 10;
         lists_after_set_state();
         if (stale || !(dual || lazy_single)) { vel_check_due = false; rebuild(first_step); return; }
-        if ((check_due(first_step, every) && first_step != last_build_step) || vel_check_due) { vel_check_due = false; refresh(first_step); }
+        if ((check_due(first_step, rebuild_every()) && first_step != last_build_step) || vel_check_due) { vel_check_due = false; refresh(first_step); }
     }
 
     void ensure_built(int64_t step_n) {
-        const int every = cfg.rebuild_every > 0 ? cfg.rebuild_every : 10;
         resolve_track(step_n);
         lists_after_set_state();
         vel_check_due = false;   // (driven from outside there is no time step: the displacement checks of set_state are all there is)
         if (stale) rebuild(step_n);
-        else if (check_due(step_n, every) && step_n != last_build_step) refresh(step_n);
+        else if (check_due(step_n, rebuild_every()) && step_n != last_build_step) refresh(step_n);
     }
 
     // What a pruning pass leaves for the host — the pruned list's largest tile and row total, the largest displacement since the outer search — read WITHOUT draining
@@ -967,14 +989,14 @@ template <class T> class Engine final : public EngineBase {
                         const bool with_spread = fuse_spread_next;
                         const int order = with_spread ? pme.order : 5;
                         // inside vv_run: the Σ m v partials of the launch before become one partial in an extra workgroup of this launch (the step's last launch reads four words)
-                        const bool gs_cm_fin = (in_vv_fused || in_lang_fused) && !energy && cm_pending == 2 && n_cm_step > 1 && n_cm_step <= 65536;
+                        const bool gs_cm_fin = (in_vv_fused || in_lang_fused) && !energy && pending_cm.mode() == 2 && pending_cm.n > 1 && pending_cm.n <= 65536;
                         if (gs_cm_fin) cm_fin_buf.reserve(4);
                         const size_t lds = (with_spread ? std::max(gs_lds_bytes(q_lds, BI, JS / GS), std::min<size_t>((size_t)MAX_LDS_BYTES / GS, spread_head_bytes_f32(order) + (size_t)PME_BOX_BYTES)) : gs_lds_bytes(q_lds, BI, JS / GS)) & ~(size_t)15;
                         const int n_spread = with_spread ? (int)std::min<int64_t>(cdiv(n_owned, (int64_t)64), 4096) : 0;
                         launch_pair_spread_bonded(Z, n_blocks * GS, coulm, minimg, order, n_owned, reinterpret_cast<float*>(pme.rgrid.p), reinterpret_cast<const PmeP<float>&>(pme.P), n_spread,
                                                   reinterpret_cast<const BondedArgs<float>&>(static_cast<const BondedArgs<T>&>(bonded.slot_args(G, I, pos[cur].p, inv.p))), cdiv(bonded.n_blocks(), 4), lds, stream,
-                                                  gs_cm_fin ? cm_src() : (const double*)nullptr, n_cm_step, gs_cm_fin ? cm_fin_buf.p : (double*)nullptr);
-                        if (gs_cm_fin) { cm_ext = cm_fin_buf.p; n_cm_step = 1; }
+                                                  gs_cm_fin ? pending_cm.parts_arg() : (const double*)nullptr, pending_cm.n, gs_cm_fin ? cm_fin_buf.p : (double*)nullptr);
+                        if (gs_cm_fin) pending_cm.moved(cm_fin_buf.p, 1);
                         spread_fused = with_spread; terms_fused = !with_spread;
                     } else launch_forces_gs(Z, coulm, minimg, stream);
                     fuse_spread_next = fuse_terms_next = false;
@@ -1032,10 +1054,10 @@ template <class T> class Engine final : public EngineBase {
         // inside vv_run: the Σ m v partials of the integrator launch before this pass become one partial here (kernels.h, cm_finalize_in_block)
         A.cm_fin_in = nullptr; A.cm_fin_n = 0; A.cm_fin_out = nullptr;
         A.vel = nullptr; A.pos_next = nullptr; A.dt = T(0); A.dt2 = T(0); A.cm_in = nullptr; A.cm_n = 0; A.cm_pub = nullptr; A.step_seq = 0; A.cm_out = nullptr; A.trk_part = nullptr; A.snap_a = nullptr; A.snap_b = nullptr;
-        const bool cm_fin = (in_vv_fused || in_lang_fused) && !energy && n_ghost == 0 && part == 0 && cm_pending == 2 && n_cm_step > 1 && n_cm_step <= 65536;      // (the energy variants do not carry the sum)
-        if (cm_fin) { cm_fin_buf.reserve(4); A.cm_fin_in = cm_src(); A.cm_fin_n = n_cm_step; A.cm_fin_out = cm_fin_buf.p; }
+        const bool cm_fin = (in_vv_fused || in_lang_fused) && !energy && n_ghost == 0 && part == 0 && pending_cm.mode() == 2 && pending_cm.n > 1 && pending_cm.n <= 65536;      // (the energy variants do not carry the sum)
+        if (cm_fin) { cm_fin_buf.reserve(4); A.cm_fin_in = pending_cm.parts_arg(); A.cm_fin_n = pending_cm.n; A.cm_fin_out = cm_fin_buf.p; }
         else if (cm_fin_solo_src && !energy && n_ghost == 0 && part == 0 && !cm_fin_solo_done) {      // (mhip_domain_run on one brick: halo_mid's partials)
-            cm_fin_buf.reserve(4); A.cm_fin_in = cm_fin_solo_src; A.cm_fin_n = n_cm_step; A.cm_fin_out = cm_fin_buf.p; cm_fin_solo_done = true;
+            cm_fin_buf.reserve(4); A.cm_fin_in = cm_fin_solo_src; A.cm_fin_n = pending_cm.n; A.cm_fin_out = cm_fin_buf.p; cm_fin_solo_done = true;
         }
         A.level_pairs = (prune && JS == 2) ? 1 : 0;      // (an atom's two sub-lists levelled before they are padded: kernels.h)
         A.dbg = (!prune && !energy) ? stamps_begin((size_t)n_blocks * 16 * 8) : nullptr;
@@ -1043,13 +1065,13 @@ template <class T> class Engine final : public EngineBase {
         step_done = false;
         bool do_step = false;
         if constexpr (std::is_same<T, float>::value) {
-            do_step = step_req.on && fuse_step_env && fast_f32 && A.soa != 0 && use_inner && !prune && part == 0 && !frc_override && (n_ghost == 0 || halo_req.on) && cm_pending != 1;
+            do_step = step_req.on && fuse_step_env && fast_f32 && A.soa != 0 && use_inner && !prune && part == 0 && !frc_override && (n_ghost == 0 || halo_req.on) && pending_cm.mode() != 1;
             if (halo_req.on && !do_step) throw ApiError{MHIP_ERR_STATE, "internal: the fused ghosted step was asked for a pass that cannot integrate"};
             if (do_step) {
                 pos_alt.reserve(cap); cm_blk.reserve(2 * 4 * (size_t)n_blocks + 8);
                 if (!cm_pub.p) { cm_pub.reserve(4); MHIP_HIP(hipMemsetAsync(cm_pub.p, 0, 4 * sizeof(unsigned long long), stream)); }      // (launch numbers start at 1)
                 A.vel = vel[cur].p; A.pos_next = pos_alt.p; A.dt = T(step_req.dt); A.dt2 = T(step_req.dt) / T(2);
-                A.cm_in = cm_pending == 2 ? cm_src() : (const double*)nullptr; A.cm_n = n_cm_step; A.cm_pub = cm_pub.p; A.step_seq = ++step_seq;
+                A.cm_in = pending_cm.parts_arg(); A.cm_n = pending_cm.n; A.cm_pub = cm_pub.p; A.step_seq = ++step_seq;
                 A.cm_out = step_req.cm ? cm_blk.p + (size_t)step_half * 4 * n_blocks : (double*)nullptr;
                 A.trk_part = nullptr; A.snap_a = pos_snap_in.p; A.snap_b = pos_snap.p;
                 if (step_req.measure) { trk_part.reserve(3 * (size_t)std::max(n_blocks, 1024)); trk_out.reserve(4); A.trk_part = trk_part.p; }
@@ -1075,7 +1097,7 @@ template <class T> class Engine final : public EngineBase {
                 step_done = true; ++n_fused_steps; step_parts = n_blocks;
             } else launch_forces_any(A, energy);
         } else launch_forces_any(A, energy);
-        if (cm_fin && !do_step) { cm_ext = cm_fin_buf.p; n_cm_step = 1; }
+        if (cm_fin && !do_step) pending_cm.moved(cm_fin_buf.p, 1);
         tr("after k_forces");
         if constexpr (std::is_same<T, float>::value) {
             if (prune && GS > 0) {      // the list this prune wrote, dealt to the groups (it stays as it is for every other kind of pass)
@@ -1221,14 +1243,12 @@ template <class T> class Engine final : public EngineBase {
     bool halo_fused_ok(int64_t step_n) {
         if (!(xf_direct && xf.n_peers > 0 && n_ghost > 0 && hp_set && xf.routes) || replan_now) return false;
         if (hp.cm_rows != 3 || hp.n_cm_peers != xf.n_peers || (int)xf.peer_rank.size() != xf.n_peers) return false;
-        const int every = cfg.rebuild_every > 0 ? cfg.rebuild_every : 10;
-        if (check_due(step_n, every) && step_n != last_build_step && !(host_prune && inner_valid)) return false;      // (refresh() of such a step only books it)
+        if (check_due(step_n, rebuild_every()) && step_n != last_build_step && !(host_prune && inner_valid)) return false;      // (refresh() of such a step only books it)
         return packed_step_possible();
     }
     void halo_fused(int64_t step_n, double dt, bool cm, bool measure) {
-        const int every = cfg.rebuild_every > 0 ? cfg.rebuild_every : 10;
         cur_dt = dt;
-        if (check_due(step_n, every) && step_n != last_build_step && dual) refresh(step_n);
+        if (check_due(step_n, rebuild_every()) && step_n != last_build_step && dual) refresh(step_n);
         step_req.on = true; step_req.gcv = false; step_req.cm = cm; step_req.measure = measure; step_req.dt = dt;
         halo_req.on = true; halo_req.cm_in = halo_cm_in;
         step_done = false;
@@ -1237,7 +1257,7 @@ template <class T> class Engine final : public EngineBase {
         if (!step_done) throw ApiError{MHIP_ERR_STATE, "internal: the fused ghosted step did not launch"};
         step_done = false;
         if (cm) step_half ^= 1;
-        halo_cm_in = cm; frc_valid = false; pend_a = nullptr; cm_pending = 0; cm_ext = nullptr;
+        halo_cm_in = cm; frc_valid = false; pend_a = nullptr; pending_cm.none();
         hx.trk_step = measure ? step_n + 1 : -1;
         MHIP_HIP(hipGetLastError());
     }
@@ -1373,13 +1393,13 @@ template <class T> class Engine final : public EngineBase {
             frc_side.reserve(cap);
             // … and, on a mid-run step of vv_run, the integrator in that last launch (v_cm of the step before as ONE partial, or none pending)
             GcvArgs<T> V; const GcvArgs<T>* vp = nullptr;
-            if (step_req.gcv && fuse_gcv_env && !redo && (cm_pending == 0 || (cm_pending == 2 && n_cm_step == 1)) && pme.order >= 4 && pme.order <= 6) {
+            if (step_req.gcv && fuse_gcv_env && !redo && (pending_cm.mode() == 0 || (pending_cm.mode() == 2 && pending_cm.n == 1)) && pme.order >= 4 && pme.order <= 6) {
                 const int nb = (int)Pme<T>::atom_blocks(n_owned);
                 cm_blk.reserve(2 * 4 * (size_t)nb + 8);
                 if (step_req.measure) { trk_part.reserve(3 * (size_t)std::max(nb, 1024)); trk_out.reserve(4); }
                 std::memset(&V, 0, sizeof(V));
                 V.vel = vel[cur].p; V.dt = T(step_req.dt); V.dt2 = T(step_req.dt) / T(2); V.G = G;
-                V.cm_in = cm_pending == 2 ? cm_src() : (const double*)nullptr;
+                V.cm_in = pending_cm.parts_arg();
                 V.cm_out = step_req.cm ? cm_blk.p + (size_t)step_half * 4 * nb : (double*)nullptr;
                 V.snap_a = pos_snap_in.p; V.snap_b = pos_snap.p; V.trk_part = step_req.measure ? trk_part.p : (float*)nullptr;
                 if (step_req.lang) V.S = *step_req.lang;
@@ -1434,7 +1454,7 @@ template <class T> class Engine final : public EngineBase {
         hipLaunchKernelGGL(k_iota2, dim3(std::min(cdiv(n_tot, 256), 1024)), dim3(256), 0, stream, n_tot, orig[cur].p, inv.p);
         MHIP_HIP(hipMemsetAsync(frc[cur].p, 0, n_tot * sizeof(T4), stream));
         MHIP_HIP(hipGetLastError());
-        stale = true; cm_pending = 0; cm_ext = nullptr; frc_valid = false; hp_set = false; halo_cm_in = false; trk_issued = false; hx.plan_ok = false; hx.trk_step = -1;
+        stale = true; pending_cm.none(); frc_valid = false; hp_set = false; halo_cm_in = false; trk_issued = false; hx.plan_ok = false; hx.trk_step = -1;
         // the search radius depends on whether there are ghosts and on the ghost margin, the blocking on the size class: a re-plan
         // that changes neither keeps the grid, its Hilbert table and the (already adapted) capacities
         const int size_class = n_owned >= 100000 ? 2 : (n_owned >= 40000 ? 1 : 0);
@@ -1686,8 +1706,7 @@ template <class T> class Engine final : public EngineBase {
         tri_mode = approx_images ? 1 : 2;
         ljm = ljm_base;                          // the one-type LJ kernels are cubic-only
         if (pme.on()) pme.setup(pme_order_, pme_mesh_, pme_alpha_, cfg.inter.coul_ke, pme_eps_r_, cfg.box, cfg.periodic, tri_bv);   // (PME set before the boundary: its recip_box again)
-        setup_grid(); choose_blocking();
-        stale = true; frc_valid = false; state_set = false;
+        regrid(); frc_valid = false; state_set = false;
     }
     // The boundary of a LIVE context replaced (≙ `sys.boundary = scale_boundary(…)`: scale_coords!, spatial.jl:1184-1218, as the barostats of coupling.jl call it —
     // the reference's force and energy entry points read sys.boundary on every call, ext/MollyCUDAExt.jl:845, 936).  box3: the new side lengths (a TriclinicBoundary:
@@ -1703,6 +1722,8 @@ template <class T> class Engine final : public EngineBase {
             if (std::fabs(bv9[0] - box3[0]) > 1e-12 * bv9[0] || std::fabs(bv9[4] - box3[1]) > 1e-12 * bv9[4] || std::fabs(bv9[8] - box3[2]) > 1e-12 * bv9[8])
                 throw ApiError{MHIP_ERR_INVALID, "set_box: the box must be (v1.x, v2.y, v3.z) of the triclinic basis"};
         }
+        // from here on, whichever way this ends: no list, no forces, the coordinates to be handed over again
+        stale = true; frc_valid = false; frc_run_total = false; frc_before_set_state = false; state_set = false;      // (Σq, Σq² of the PME's constant terms do not depend on the box: pc_valid stays)
         flush_cm();
         MHIP_HIP(hipStreamSynchronize(stream));
         const mhip_config old_cfg = cfg; double old_bv[9]; std::memcpy(old_bv, tri_bv, sizeof(old_bv));
@@ -1713,13 +1734,11 @@ template <class T> class Engine final : public EngineBase {
             setup_grid(); choose_blocking();
             size_t tb2 = 0; MHIP_HIP(exclusive_sum_i32(nullptr, tb2, cell_cnt.p, cell_start.p, 2 * G.ncell + 1, stream));
             if (tb2 + 256 > cub_tmp.n) cub_tmp.reserve(tb2 + 256);
-        } catch (...) {      // (a box the engine cannot take — r_list beyond half a side with exact images off, a mesh the PME refuses: the context stays what it was)
+        } catch (...) {      // (a HIP allocation or copy that failed: back to the old box; the caller gets this first error, whatever the way back meets)
             cfg = old_cfg; std::memcpy(tri_bv, old_bv, sizeof(tri_bv));
-            pme.rebox(pme_alpha_, cfg.inter.coul_ke, pme_eps_r_, cfg.box, tri_mode ? tri_bv : nullptr);
-            setup_grid(); choose_blocking(); stale = true; frc_valid = false; state_set = false;
+            try { pme.rebox(pme_alpha_, cfg.inter.coul_ke, pme_eps_r_, cfg.box, tri_mode ? tri_bv : nullptr); regrid(); } catch (...) {}
             throw;
         }
-        stale = true; frc_valid = false; frc_run_total = false; frc_before_set_state = false; state_set = false;      // (Σq, Σq² of the PME's constant terms do not depend on the box: pc_valid stays)
         ++n_box_changes;
     }
     int64_t n_box_changes = 0;
@@ -1776,7 +1795,7 @@ template <class T> class Engine final : public EngineBase {
         flush_cm();
         cm_partials_now();
         hipLaunchKernelGGL(k_cm_finalize<T>, dim3(1), dim3(256), 0, stream, cdiv(n_owned, 256), (const double*)red_part.p, red_out.p, vcm.p);
-        cm_pending = 1; flush_cm();
+        pending_cm.subtract(); flush_cm();
         MHIP_HIP(hipGetLastError());
     }
 
@@ -1794,7 +1813,7 @@ template <class T> class Engine final : public EngineBase {
         T h[3] = {T(dv3[0]), T(dv3[1]), T(dv3[2])};
         MHIP_HIP(hipMemcpyAsync(vcm.p, h, 3 * sizeof(T), hipMemcpyHostToDevice, stream));
         MHIP_HIP(hipStreamSynchronize(stream));
-        cm_pending = 1; flush_cm();
+        pending_cm.subtract(); flush_cm();
     }
 
     void cm_momentum_dev(double* out4_dev) override {
@@ -1806,7 +1825,7 @@ template <class T> class Engine final : public EngineBase {
     void remove_cm_dev(const double* total4_dev) override {
         flush_cm();
         // {ΣPx, ΣPy, ΣPz, ΣM} is read as ONE partial by the next k_vv1 (or any state read): total4_dev must stay untouched until then
-        cm_ext = total4_dev; n_cm_step = 1; cm_pending = 2;
+        pending_cm.resum(total4_dev, 1);
     }
 
     void check_finite() override {
@@ -1842,9 +1861,9 @@ template <class T> class Engine final : public EngineBase {
         tr("k_vv1");
         prof.begin(2, stream);
         hipLaunchKernelGGL(k_vv1<T>, dim3(std::min(cdiv(n_owned, 256), 1024)), dim3(256), 0, stream, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, T(dt), T(dt) / T(2),
-                           cm_pending == 1 ? (const T*)vcm.p : (const T*)nullptr, cm_pending == 2 ? cm_src() : (const double*)nullptr, n_cm_step, G);
+                           pending_cm.vcm_arg(vcm.p), pending_cm.parts_arg(), pending_cm.n, G);
         prof.end(2, stream);
-        cm_pending = 0; cm_ext = nullptr;
+        pending_cm.none();
     }
     void stage2_impl(int64_t step_n, double dt, bool cm, double* cm_parts_ext = nullptr, int n_parts_ext = 0) {
         step_forces(step_n);
@@ -1854,7 +1873,7 @@ template <class T> class Engine final : public EngineBase {
         prof.begin(2, stream);
         if (cm) {
             hipLaunchKernelGGL((k_vv2<T, true>), dim3(nb), dim3(256), 0, stream, n_owned, vel[cur].p, frc[cur].p, T(dt) / T(2), cm_parts_ext ? cm_parts_ext : cm_step.p, pend_a);
-            cm_pending = 2; n_cm_step = nb;   // the next k_vv1 (or any flush) re-sums the partials: no finalize launch
+            pending_cm.resum(cm_step.p, nb);   // the next k_vv1 (or any flush) re-sums the partials: no finalize launch (those in cm_parts_ext: halo_end_parts drops this at once)
         } else {
             hipLaunchKernelGGL((k_vv2<T, false>), dim3(nb), dim3(256), 0, stream, n_owned, vel[cur].p, frc[cur].p, T(dt) / T(2), (double*)nullptr, pend_a);
         }
@@ -1864,9 +1883,8 @@ template <class T> class Engine final : public EngineBase {
     // the neighbour cadence of a stepwise-driven run: as in vv_run.  A ghosted sub-domain without the dual list is re-planned
     // (set_atom_counts / set_state → stale) by the host at every rebuild step instead.
     void stage2_cadenced(int64_t step_n, double dt, bool cm, double* cm_parts_ext = nullptr, int n_parts_ext = 0) {
-        const int every = cfg.rebuild_every > 0 ? cfg.rebuild_every : 10;
         resolve_track(step_n);
-        const bool due = check_due(step_n, every) && step_n != last_build_step && (n_ghost == 0 || dual);
+        const bool due = check_due(step_n, rebuild_every()) && step_n != last_build_step && (n_ghost == 0 || dual);
         if (due && dual) refresh(step_n);
         stage2_impl(step_n, dt, cm, cm_parts_ext, n_parts_ext);
         if (due && !dual) refresh(step_n);
@@ -1882,13 +1900,13 @@ template <class T> class Engine final : public EngineBase {
         if (cm_parts_dev && (n_parts < 1 || n_parts > 1024)) throw ApiError{MHIP_ERR_INVALID, "n_parts must be 1..1024"};
         scatter_coords(first, n, in_dev);
         stage2_cadenced(step_n, dt, cm_parts_dev != nullptr, cm_parts_dev, n_parts);
-        if (cm_parts_dev) { cm_pending = 0; cm_ext = nullptr; }
+        if (cm_parts_dev) pending_cm.none();
         MHIP_HIP(hipGetLastError());
     }
     void remove_cm_parts_dev(const double* total_parts_dev, int32_t n_parts) override {
         if (n_parts < 1 || n_parts > 1024) throw ApiError{MHIP_ERR_INVALID, "n_parts must be 1..1024"};
         flush_cm();
-        cm_ext = total_parts_dev; n_cm_step = n_parts; cm_pending = 2;
+        pending_cm.resum(total_parts_dev, n_parts);
     }
 
     void set_ghost_margin(double m) override {
@@ -1936,10 +1954,10 @@ template <class T> class Engine final : public EngineBase {
     // that nothing waits for them): the drift bounds then reach that much further
     int plan_decide_late(int64_t step_n, const float* red3, int32_t* check_in, int late) {
         if (check_in) *check_in = 0;
-        const int every = cfg.rebuild_every > 0 ? cfg.rebuild_every : 10;
+        const int every = rebuild_every();
         if (!engine_sched) {   // first use: from now on the inner list may be tighter than r_list
             engine_sched = true;
-            skin_in = std::min(skin, std::max(1, env_int("MOLLYHIP_INNER_SKIN_PM", 100)) * 1e-3);
+            skin_in = std::min(skin, inner_skin_floor());
             const T rp = T(rc_max_ + skin_in);
             r_prune2 = (skin_in < skin) ? rp * rp : r_in2;
         }
@@ -1989,7 +2007,7 @@ template <class T> class Engine final : public EngineBase {
             X.peers = xf.d_peers.p; X.n_peers = xf.n_peers; X.done = xf.done.p;
         }
         hipLaunchKernelGGL(k_halo_pack<T>, dim3(cdiv(std::max<int64_t>(hp.n_send_rows, 1), 256) + 1), dim3(256), 0, stream, hp.n_send_rows, hp.send_idx, (const T*)hp.send_shift, (const int32_t*)inv.p,
-                           (const T4*)pos[cur].p, (T*)hp.send, with_cm ? (const double*)cm_step.p : (const double*)nullptr, n_cm_step, hp.send_cm_pos, hp.n_send_cm, std::max(hp.cm_rows, 1), cm_all.p, X);
+                           (const T4*)pos[cur].p, (T*)hp.send, with_cm ? (const double*)cm_step.p : (const double*)nullptr, pending_cm.n, hp.send_cm_pos, hp.n_send_cm, std::max(hp.cm_rows, 1), cm_all.p, X);
         MHIP_HIP(hipGetLastError());
     }
     // first kick + drift + pack: after vv_init, after a step that stopped behind its second kick, after a re-plan
@@ -2017,19 +2035,18 @@ template <class T> class Engine final : public EngineBase {
         }
         cur_dt = dt;
         if (replan_now) { replan_now = false; device_replan(step_n); }            // (mhip_domain_run: ownership, ghosts and the outer list redone here, in front of the step's force pass)
-        const int every = cfg.rebuild_every > 0 ? cfg.rebuild_every : 10;
-        const bool due = check_due(step_n, every) && step_n != last_build_step && (n_ghost == 0 || dual);
+        const bool due = check_due(step_n, rebuild_every()) && step_n != last_build_step && (n_ghost == 0 || dual);
         if (due && dual) refresh(step_n);
         const bool solo = hp.n_cm_peers == 0 && hp.n_send_rows == 0;              // no peers: the partials of the launch before are the whole sum
         // … which workgroup 0 of the pair pass in between adds up into ONE partial, as inside mhip_vv_run (ForceArgs::cm_fin_in): the integrator's blocks
         // then do not each re-sum hundreds of partials first
-        cm_fin_solo_src = (solo && halo_cm_in && n_ghost == 0 && n_cm_step > 1 && n_cm_step <= 4096) ? (const double*)cm_step.p + (size_t)(cm_half ^ 1) * 4 * 1024 : (const double*)nullptr;
+        cm_fin_solo_src = (solo && halo_cm_in && n_ghost == 0 && pending_cm.n > 1 && pending_cm.n <= 4096) ? (const double*)cm_step.p + (size_t)(cm_half ^ 1) * 4 * 1024 : (const double*)nullptr;
         cm_fin_solo_done = false;
         step_forces(step_n);
         cm_fin_solo_src = nullptr;
-        if (cm_pending) flush_cm();                                               // (a removal registered through the stepwise entry points)
+        flush_cm();                                                               // (a removal registered through the stepwise entry points)
         const double* cm_in = halo_cm_in ? (solo ? (cm_fin_solo_done ? (const double*)cm_fin_buf.p : (const double*)cm_step.p + (size_t)(cm_half ^ 1) * 4 * 1024) : (const double*)cm_all.p) : (const double*)nullptr;
-        const int n_in = solo ? (cm_fin_solo_done ? 1 : n_cm_step) : 1 + hp.n_cm_peers;
+        const int n_in = solo ? (cm_fin_solo_done ? 1 : pending_cm.n) : 1 + hp.n_cm_peers;
         // (block count: mhip_vv_run's — fewer, longer blocks at these sizes, see there)
         const int nb = (cm && last) ? n_parts : std::min(cdiv(n_owned, 256), solo ? (int)std::max<int64_t>(256, std::min<int64_t>(512, n_owned / 2048)) : 1024);
         double* cm_out = cm ? (last ? cm_parts_dev : cm_step.p + (size_t)(solo ? cm_half : 0) * 4 * 1024) : (double*)nullptr;
@@ -2042,10 +2059,10 @@ template <class T> class Engine final : public EngineBase {
         if (last) { if (cm) go(k_vv_mid<T, true, true>); else go(k_vv_mid<T, false, true>); }
         else { if (cm) go(k_vv_mid<T, true, false>); else go(k_vv_mid<T, false, false>); }
         prof.end(2, stream);
-        pend_a = nullptr; cm_pending = 0; cm_ext = nullptr;
+        pend_a = nullptr; pending_cm.none();
         if (due && !dual) refresh(step_n);
         if (!last) {
-            n_cm_step = nb;
+            pending_cm.n = nb;
             if (solo) cm_half ^= 1; else halo_pack(cm);
             halo_cm_in = cm;
             frc_valid = false;                                                    // frc[cur] belongs to the coordinates before the drift
@@ -2216,7 +2233,7 @@ template <class T> class Engine final : public EngineBase {
         if (!xf.h_red3) { MHIP_HIP(hipHostMalloc((void**)&xf.h_red3, 4 * sizeof(float))); MHIP_HIP(hipEventCreateWithFlags(&xf.ev_plan, hipEventDisableTiming)); xf.mine3.reserve(4); xf.world = std::max(xf.world, 1); }
         *steps_done = 0; *reason = 0;
         if (n_steps <= 0) return;
-        const int every = cfg.rebuild_every > 0 ? cfg.rebuild_every : 10;
+        const int every = rebuild_every();
         const int64_t last = first_step + n_steps;
         InRun guard_in_run(in_run);
         if (solo && n_ghost == 0 && xf.world <= 1) {
@@ -2224,7 +2241,7 @@ template <class T> class Engine final : public EngineBase {
             // launches), with the lists kept by the engine's own criteria.  The run's last Σ m v goes to cm_parts_dev for the caller's (one-rank) sum.
             if (host_prune) {      // (set_ghost_margin handed the prune decisions to a host that has no peers to agree with)
                 host_prune = false; engine_sched = true;
-                skin_in = std::min(skin, std::max(skin_in_adapted, std::max(1, env_int("MOLLYHIP_INNER_SKIN_PM", 100)) * 1e-3));
+                skin_in = std::min(skin, std::max(skin_in_adapted, inner_skin_floor()));
                 const T rp = T(rc_max_ + skin_in);
                 r_prune2 = (skin_in < skin) ? rp * rp : r_in2;
                 inner_valid = false;
@@ -2511,8 +2528,7 @@ template <class T> class Engine final : public EngineBase {
     // pending); returns 1 if it launched, 0 if halo_end will do the whole pass.
     int halo_interior(int64_t step_n) override {
         interior_done = false;
-        const int every = cfg.rebuild_every > 0 ? cfg.rebuild_every : 10;
-        if (n_ghost == 0 || stale || !frc_valid_for_split() || (step_n % every == 0 && step_n != last_build_step)) return 0;
+        if (n_ghost == 0 || stale || !frc_valid_for_split() || (step_n % rebuild_every() == 0 && step_n != last_build_step)) return 0;
         launch_pair_kernel(false, 1);
         interior_done = true;
         return 1;
@@ -2522,12 +2538,21 @@ template <class T> class Engine final : public EngineBase {
         scatter_coords(first, n, in_dev);
         stage2_cadenced(step_n, dt, cm_out4_dev != nullptr);
         if (cm_out4_dev) {   // this rank's {ΣPx, ΣPy, ΣPz, ΣM} for the all-reduce; nothing pending locally: the TOTAL comes back via remove_cm_dev
-            hipLaunchKernelGGL(k_cm_finalize<T>, dim3(1), dim3(256), 0, stream, n_cm_step, (const double*)cm_step.p, cm_out4_dev, (T*)nullptr);
-            cm_pending = 0;
+            hipLaunchKernelGGL(k_cm_finalize<T>, dim3(1), dim3(256), 0, stream, pending_cm.n, (const double*)cm_step.p, cm_out4_dev, (T*)nullptr);
+            pending_cm.none();
         }
         MHIP_HIP(hipGetLastError());
     }
     void rebuild_now(int64_t step_n) override { flush_cm(); resolve_track(step_n); lists_after_set_state(); if (stale) rebuild(step_n); else refresh(step_n); }
+
+    // the tail of a step whose force pass integrated (step_done, of vv_loop and langevin_run): the check it measured is issued for trk_at, the Σ m v
+    // partials it left in cm_blk are pending removal, frc[cur] belongs to the coordinates before the drift
+    void after_fused_step(bool measure, int64_t trk_at, bool cm) {
+        step_done = false;
+        if (measure) issue_track(step_parts, trk_at);
+        pend_a = nullptr; pending_cm.none(); frc_valid = false;
+        if (cm) { pending_cm.resum(cm_blk.p + (size_t)step_half * 4 * step_parts, step_parts); step_half ^= 1; }
+    }
 
     void vv_run(int64_t first_step, int64_t n_steps, double dt, int remove_cm_every) override {
         if (!state_set || !params_set) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before vv_run"};
@@ -2544,7 +2569,7 @@ template <class T> class Engine final : public EngineBase {
     // the step loop of a single domain: forces of first_step are in place.  cm_parts_last (nullable): where the LAST step leaves its Σ m v partials (n_parts_last
     // blocks) instead of registering their removal with the context — mhip_domain_run on one brick, whose caller sums them over the (one) rank.
     void vv_loop(int64_t first_step, int64_t n_steps, double dt, int remove_cm_every, double* cm_parts_last, int n_parts_last) {
-        const int every = cfg.rebuild_every > 0 ? cfg.rebuild_every : 10;
+        const int every = rebuild_every();
         // fused stepping: first kick + drift once, then ONE integrator launch between consecutive force passes (k_vv_mid), the
         // plain second kick at the end.  A thermostat needs v_n between the kicks: the two-launch form then.
         const bool fused = !(andersen_prob > 0);
@@ -2576,17 +2601,7 @@ template <class T> class Engine final : public EngineBase {
             step_forces(step);
             step_req.on = step_req.gcv = false;
             if (step_done) {      // the pair pass integrated on the way (k_forces STEP): no integrator launch for this step
-                step_done = false;
-                if (measure) {
-                    if (!h_trk) MHIP_HIP(hipHostMalloc((void**)&h_trk, 4 * sizeof(float)));
-                    if (!ev_trk) MHIP_HIP(hipEventCreateWithFlags(&ev_trk, hipEventDisableTiming));
-                    hipLaunchKernelGGL(k_track_reduce, dim3(1), dim3(256), 0, stream, step_parts, (const float*)trk_part.p, trk_out.p, h_trk);
-                    MHIP_HIP(hipEventRecord(ev_trk, stream));
-                    trk_issued = true; trk_step = step + 1; trk_prev_vmax = last_vmax; trk_prune_id = n_filters; trk_outer_id = n_outer;
-                }
-                pend_a = nullptr; cm_pending = 0; cm_ext = nullptr;
-                if (cm) { cm_pending = 2; cm_ext = cm_blk.p + (size_t)step_half * 4 * step_parts; n_cm_step = step_parts; step_half ^= 1; }
-                frc_valid = false;
+                after_fused_step(measure, step + 1, cm);
                 continue;
             }
             if (!pre && check_due(step, every)) { fold_side_forces(); refresh(step); }   // the sort permutes vel / frc with the atoms; Σ m v does not care
@@ -2595,7 +2610,7 @@ template <class T> class Engine final : public EngineBase {
             // 1M atoms: 21.2 → 20.2 µs with 512, 21.8 with 256)
             const bool parts_out = step == last && cm && cm_parts_last != nullptr;
             const int nb = parts_out ? n_parts_last : std::min(cdiv(n_owned, 256), (int)std::max<int64_t>(256, std::min<int64_t>(512, n_owned / 2048)));
-            const double* cm_in = cm_pending == 2 ? cm_src() : (const double*)nullptr;
+            const double* cm_in = pending_cm.parts_arg();
             double* cm_out = cm ? (parts_out ? cm_parts_last : cm_step.p + (size_t)half * 4 * 1024) : (double*)nullptr;
             prof.begin(2, stream);
             // the speeds for a check that the next step's force pass will measure (see resolve_track); evaluated behind the pass: a prune inside it makes the lists checkable again
@@ -2603,23 +2618,16 @@ template <class T> class Engine final : public EngineBase {
             if (measure_mid) { trk_part.reserve(3 * (size_t)std::max(n_blocks, 1024)); trk_out.reserve(4); }
             auto go = [&](auto kern) {
                 hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, stream, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, T(dt), T(dt) / T(2),
-                                   cm_in, n_cm_step, cm_out, (const T4*)pend_a, G,
+                                   cm_in, pending_cm.n, cm_out, (const T4*)pend_a, G,
                                    measure_mid ? (const T4*)pos_snap_in.p : (const T4*)nullptr, measure_mid ? (const T4*)pos_snap.p : (const T4*)nullptr, measure_mid ? trk_part.p : (float*)nullptr);
             };
             if (step == last) { if (cm) go(k_vv_mid<T, true, true>); else go(k_vv_mid<T, false, true>); }
             else { if (cm) go(k_vv_mid<T, true, false>); else go(k_vv_mid<T, false, false>); }
             prof.end(2, stream);
-            if (measure_mid) {   // the check of step + 1: reduce, copy, event — read by resolve_track at step + 2
-                if (!h_trk) MHIP_HIP(hipHostMalloc((void**)&h_trk, 4 * sizeof(float)));
-                if (!ev_trk) MHIP_HIP(hipEventCreateWithFlags(&ev_trk, hipEventDisableTiming));
-                hipLaunchKernelGGL(k_track_reduce, dim3(1), dim3(256), 0, stream, nb, (const float*)trk_part.p, trk_out.p, h_trk);   // (straight into pinned host memory)
-                MHIP_HIP(hipEventRecord(ev_trk, stream));
-                trk_issued = true; trk_step = step + 1; trk_prev_vmax = last_vmax; trk_prune_id = n_filters; trk_outer_id = n_outer;
-            }
+            if (measure_mid) issue_track(nb, step + 1);   // the check of step + 1, read by resolve_track at step + 2
             if (step == last) frc_run_total = pend_a == nullptr && n_ghost == 0;   // (side arrays are added by the kick, not folded)
-            pend_a = nullptr;
-            cm_pending = 0; cm_ext = nullptr;
-            if (cm && !parts_out) { cm_pending = 2; cm_ext = cm_out; n_cm_step = nb; half ^= 1; }
+            pend_a = nullptr; pending_cm.none();
+            if (cm && !parts_out) { pending_cm.resum(cm_out, nb); half ^= 1; }
             if (step != last) frc_valid = false;                                  // frc[cur] belongs to the coordinates before the drift
         }
     }
@@ -2639,9 +2647,8 @@ template <class T> class Engine final : public EngineBase {
         StochP<T> P = stoch_params(kT, key, ctr1);
         const double pc = std::min(std::max(prob, 0.0), std::nextafter(1.0, 0.0));          // clamp(…, 0, prevfloat(1.0))
         P.prob_u64 = (uint64_t)std::nearbyint(std::ldexp(pc, 64));                            // round(UInt64, prob·2⁶⁴) ≤ 2⁶⁴ − 2¹¹
-        launch_redraw<T>(stream, mode, n_owned, vel[cur].p, orig[cur].p, P, cm_pending == 1 ? (const T*)vcm.p : (const T*)nullptr,
-                         cm_pending == 2 ? cm_src() : (const double*)nullptr, n_cm_step);
-        cm_pending = 0; cm_ext = nullptr;
+        launch_redraw<T>(stream, mode, n_owned, vel[cur].p, orig[cur].p, P, pending_cm.vcm_arg(vcm.p), pending_cm.parts_arg(), pending_cm.n);
+        pending_cm.none();
         MHIP_HIP(hipGetLastError());
     }
     // AndersenThermostat as the coupling of vv_run / langevin_run: applied after every step's CM removal (simulators.jl:630, 1209);
@@ -2661,7 +2668,7 @@ template <class T> class Engine final : public EngineBase {
         if (!state_set || !params_set) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before langevin_run"};
         if (n_ghost > 0) throw ApiError{MHIP_ERR_STATE, "langevin_run is single-domain"};
         if (!(kT >= 0) || !(friction >= 0)) throw ApiError{MHIP_ERR_INVALID, "temperature and friction must be non-negative"};
-        const int every = cfg.rebuild_every > 0 ? cfg.rebuild_every : 10;
+        const int every = rebuild_every();
         cur_dt = dt;
         InRun guard_in_run(in_run);
         InRun guard_lang(in_lang_fused); in_lang_fused = bonded.any() && pme.on() && fuse_gcv_env;
@@ -2687,16 +2694,7 @@ template <class T> class Engine final : public EngineBase {
             step_forces(step);                                                    // :1173
             step_req.gcv = step_req.on = false; step_req.lang = nullptr; step_req.measure = false;
             if (step_done) {
-                step_done = false;
-                if (measure) {
-                    if (!h_trk) MHIP_HIP(hipHostMalloc((void**)&h_trk, 4 * sizeof(float)));
-                    if (!ev_trk) MHIP_HIP(hipEventCreateWithFlags(&ev_trk, hipEventDisableTiming));
-                    hipLaunchKernelGGL(k_track_reduce, dim3(1), dim3(256), 0, stream, step_parts, (const float*)trk_part.p, trk_out.p, h_trk);
-                    MHIP_HIP(hipEventRecord(ev_trk, stream));
-                    trk_issued = true; trk_step = step; trk_prev_vmax = last_vmax; trk_prune_id = n_filters; trk_outer_id = n_outer;
-                }
-                pend_a = nullptr; cm_pending = 0; cm_ext = nullptr; frc_valid = false;
-                if (cm) { cm_pending = 2; cm_ext = cm_blk.p + (size_t)step_half * 4 * step_parts; n_cm_step = step_parts; step_half ^= 1; }
+                after_fused_step(measure, step, cm);
                 apply_coupling(step);
                 if (check_due(step, every)) refresh(step);
                 continue;
@@ -2704,12 +2702,11 @@ template <class T> class Engine final : public EngineBase {
             prof.begin(2, stream);
             double* cm_out = cm ? cm_step.p + (size_t)half * 4 * 1024 : (double*)nullptr;   // the other half may still be read by this launch
             launch_langevin<T>(stream, nb, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, orig[cur].p, P,
-                               cm_pending == 1 ? (const T*)vcm.p : (const T*)nullptr, cm_pending == 2 ? cm_src() : (const double*)nullptr, n_cm_step,
+                               pending_cm.vcm_arg(vcm.p), pending_cm.parts_arg(), pending_cm.n,
                                cm_out, G, (const T4*)pend_a);      // (the side array of a small system's step is added by the update itself, as k_vv_mid does: no k_add_forces launch)
             prof.end(2, stream);
-            pend_a = nullptr;
-            cm_pending = 0; cm_ext = nullptr; frc_valid = false;
-            if (cm) { cm_pending = 2; cm_ext = cm_out; n_cm_step = nb; half ^= 1; }   // :1204-1206, subtracted by the next consumer
+            pend_a = nullptr; pending_cm.none(); frc_valid = false;
+            if (cm) { pending_cm.resum(cm_out, nb); half ^= 1; }   // :1204-1206, subtracted by the next consumer
             apply_coupling(step);                                                 // :1208
             if (check_due(step, every)) refresh(step);                            // :1211 — the next force pass prunes the fresh outer list
         }

@@ -203,7 +203,7 @@ def test_set_box_refusals(pkg):
     import ctypes as C
     case, dtype = make("lj_fp64")
     s = case.system(pkg, dtype)
-    pkg.forces(s)
+    f0 = pkg.forces(s)
     L = pkg.lib()
     box = (C.c_double * 3)(4.0, 4.0, -1.0)
     assert L.mhip_set_box(s.engine(), box, None) == -1 and b"positive" in L.mhip_last_error(s.engine())                  # MHIP_ERR_INVALID
@@ -216,6 +216,7 @@ def test_set_box_refusals(pkg):
     # the context is still good, on its old box
     f = pkg.forces(s)
     assert np.isfinite(f).all()
+    assert np.array_equal(f, f0)                                                                                         # refused calls left the context as it was
     # forces without handing the coordinates over again: refused
     box = (C.c_double * 3)(*[float(v) * 1.01 for v in s.boundary.side_lengths])
     assert L.mhip_set_box(s.engine(), box, None) == 0
