@@ -1,7 +1,8 @@
-"""The C ABI driven by a C program (tests/c_client/mhip_drive.c, gcc, no Python in the call path): create → set_atoms → set_state →
+"""The C ABI driven by C programs (tests/c_client/mhip_drive.c and mhip_drive_topology.c, gcc, no Python in the call path): create → set_atoms → set_state →
 forces / energies → vv_run → get_state → set_state + forces(step_n) × 5 → stats → set_box (a trial move and back) → destroy.  Its numbers are checked against the CPU
 oracle on the same inputs: fp64 forces and energies at the reference's bars (test/protein.jl:267, 274), the 20-step trajectory at
-1e-9 nm, and the drop-in cadence (no new neighbour search for unchanged coordinates)."""
+1e-9 nm, and the drop-in cadence (no new neighbour search for unchanged coordinates).  The second program makes the set-up calls of the Julia shim for a
+protein (exceptions, bonded terms, Ewald exclusions, PME) and the neighbour export, CM removal, random velocities and Langevin run after them."""
 import os
 import subprocess
 
@@ -54,3 +55,85 @@ def test_c_client_drives_the_engine(tmp_path):
                 mass=np.full(n, 39.948)).oracle(np.float64)
     assert pe_scaled == pytest.approx(o3.potential_energy(o3.neighbors("cell")), rel=1e-10, abs=1e-6)
     assert pe_back == pytest.approx(pe1, rel=1e-11)
+
+
+def _topology_input(pkg, case, path, rv, lang):
+    """the input file of tests/c_client/mhip_drive_topology.c (layout in its header comment): the System's own arrays, as the shim hands them over"""
+    from molly_jl_amd import _lib
+    import ctypes as C
+    s = case.system(pkg, np.float64)
+    nf, gi = s.neighbor_finder, s.general_inters[0]
+    cfg = _lib.Config()                                        # what System.engine() fills in (api.py)
+    cfg.precision, cfg.device_id, cfg.n_atoms = 64, 0, len(s)
+    for d in range(3):
+        cfg.box[d] = s.boundary.side_lengths[d]; cfg.periodic[d] = 1
+    cfg.rebuild_every, cfg.r_list, cfg.inter = nf.n_steps, nf.dist_cutoff, s.interactions()
+    sil = {type(x).__name__: x for x in s.specific_inter_lists}
+    b, a, t, w = sil["HarmonicBonds"], sil["HarmonicAngles"], sil["PeriodicTorsions"], sil["EwaldExclusions"]
+    hdr = np.zeros(20, np.uint64)
+    for k, val in enumerate([C.sizeof(cfg), len(s), len(nf.excluded), len(nf.special), len(b.i), len(a.i), len(t.i), len(w.i), gi.order, *gi.mesh_dims,
+                             lang["n_steps"], rv["key"], rv["ctr1"], lang["key"], lang["ctr1"]]):
+        hdr[k] = np.uint64(val)
+    dh = np.zeros(8)
+    dh[:6] = [gi.α, gi.ϵr, rv["kT"], lang["dt"], lang["kT"], lang["friction"]]
+    i32 = lambda *xs: [np.ascontiguousarray(x, dtype=np.int32) for x in xs]
+    f64 = lambda *xs: [np.ascontiguousarray(x, dtype=np.float64) for x in xs]
+    parts = [hdr, dh, np.frombuffer(C.string_at(C.addressof(cfg), C.sizeof(cfg)), np.uint8),
+             *f64(s.coords, s.velocities, s.charge, s.σ, s.ϵ, s.masses), *i32(nf.excluded[:, 0], nf.excluded[:, 1], nf.special[:, 0], nf.special[:, 1]),
+             *i32(b.i, b.j), *f64(b.k, b.r0), *i32(a.i, a.j, a.k), *f64(a.kθ, a.θ0), *i32(t.i, t.j, t.k, t.l, t.periodicity), *f64(t.phase, t.k0),
+             *i32(w.i, w.j)]
+    with open(path, "wb") as fh:
+        for p in parts:
+            fh.write(np.ascontiguousarray(p).tobytes())
+
+
+def test_c_client_makes_the_shims_topology_calls(pkg, tmp_path):
+    """The set-up calls the shim makes for a real protein (exceptions, bonded terms, Ewald exclusions, PME), the neighbour export, the force parts
+    accumulated into one buffer, the three energies, CM removal, random velocities and a Langevin run — from C, on 6mrr (Ewald with exact erfc + bonded
+    + PME, fp64).  The pair set against the oracle's, forces and energy against OpenMM at test_all_pme_vs_openmm_fp64's bars, the velocities against
+    the oracle with the same Philox words, the Langevin end state at test_langevin_fp64_6mrr_pme_matches_oracle's bars."""
+    from tests import golden6mrr as G
+    from tests.test_gpu_stochastic import draws
+    from tests.test_oracle_stochastic import KB
+    exe, inp, out = tmp_path / "mhip_drive_topology", tmp_path / "in.bin", tmp_path / "out.bin"
+    lib_dir = os.path.join(ROOT, "molly.jl_amd")
+    cc = subprocess.run(["gcc", "-std=c99", "-O2", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "c_client", "mhip_drive_topology.c"),
+                         "-o", str(exe), "-L", lib_dir, "-l:libmollyhip.so", f"-Wl,-rpath,{lib_dir}", "-Wl,--allow-shlib-undefined", "-lm"], capture_output=True, text=True)
+    assert cc.returncode == 0 and "warning" not in cc.stderr, cc.stderr
+    case = G.case("ewald", np.float64, bonded=True, approx_erfc=False, pme=True)
+    n = case.n
+    ctr1_rv, key_rv = draws(31, 2)
+    key_l, ctr1_l = draws(32, 2)
+    rv = dict(kT=KB * 300.0, key=key_rv, ctr1=ctr1_rv)
+    lang = dict(n_steps=10, dt=0.0005, kT=KB * 300.0, friction=1.0, key=key_l, ctr1=ctr1_l)
+    _topology_input(pkg, case, inp, rv, lang)
+    r = subprocess.run([str(exe), str(inp), str(out)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr + r.stdout
+
+    raw = out.read_bytes()
+    n_pairs = int(np.frombuffer(raw, np.int64, 1)[0]); off = 8
+    pi = np.frombuffer(raw, np.int32, n_pairs, off); off += 4 * n_pairs
+    pj = np.frombuffer(raw, np.int32, n_pairs, off); off += 4 * n_pairs
+    psp = np.frombuffer(raw, np.uint8, n_pairs, off); off += n_pairs
+    rest = np.frombuffer(raw, np.float64, offset=off)
+    assert rest.size == 15 * n + 3
+    f = rest[:3 * n].reshape(n, 3); pe = rest[3 * n:3 * n + 3]
+    v_cm, v_rand, x_end, v_end = rest[3 * n + 3:].reshape(4, n, 3)
+
+    o = case.oracle(np.float64)
+    oi, oj, osp = o.neighbors("cell", nthreads=8)
+    a, b = S.sorted_pairs(oi, oj, osp), S.sorted_pairs(pi, pj, psp)
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+    assert n_pairs == 4602420 and int(psp.sum()) == 3094                                  # test_gpu_6mrr.py, test/basic.jl:592-593
+    d = G.data()
+    assert np.linalg.norm(f - d["openmm_forces_all_pme_exact"], axis=1).max() < 1e-6
+    assert abs(pe.sum() + G.lj_dispersion_correction(d) - float(d["openmm_energy_all_pme_exact"])) < 1e-4
+    o.remove_cm()
+    assert np.abs(v_cm - o.vel).max() < 1e-12
+    o.random_velocities(rv["kT"], key=key_rv, ctr1=ctr1_rv)
+    assert np.abs(v_rand - o.vel).max() < 6e-13 * np.sqrt(rv["kT"] / case.mass.min())     # test_random_velocities_and_andersen_match_the_oracle
+    ol = case.oracle(np.float64, velocities=v_rand)
+    ol.langevin_run(lang["n_steps"], lang["dt"], lang["kT"], lang["friction"], key=key_l, ctr1=ctr1_l, remove_cm_every=1, nthreads=8, specific=True, general=True)
+    dx = x_end - ol.coords
+    dx -= np.round(dx / case.box) * case.box
+    assert np.abs(dx).max() < 1e-9 and np.abs(v_end - ol.vel).max() < 1e-6
