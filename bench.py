@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """bench.py — ns/day (and Matom-steps/s) of the MI355X nonbonded engine on BASELINE.json's workloads.
 
-    python bench.py --gpus N --steps K --warmup W [--workload lj1m|lj256k|6mrr_pme|6mrr_direct|6mrr_rf64|6mrr_rf32|argon4096|memlimit] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload lj1m|lj256k|6mrr_pme|6mrr_direct|6mrr_rf64|6mrr_rf32|argon4096|memlimit] [--dump-outputs DIR] [--full]
 
 One "step" = one velocity-Verlet MD step (forces + integration + amortised neighbour-list upkeep) of the whole
 system, state resident in HBM.  N = 1: the whole box on one GPU.  N > 1 (launched by torch.distributed.run,
 one rank per GPU): the same box cut into spatial bricks with RCCL ghost-coordinate exchange — total work is
-fixed, so scaling is "strong".  Rank 0 prints ONE JSON line.  At N = 1 with the default workload (the 1M-atom LJ
-fluid) the line also carries, under "secondary", complete records of the metric's other configurations that fit
-one GPU: 6mrr with PME (BASELINE.json configs[2]) and the 256k-atom LJ fluid (configs[1]).
+fixed, so scaling is "strong".  Rank 0 prints ONE JSON line.
+
+A plain run at N = 1 does only what the headline needs: set-up, equilibration and warm-up, the K timed steps, the
+dump, the record.  --full adds everything else the benchmark measures: the hipEvent-timed profiling pass behind
+`roofline`, the rocprofv3 traffic passes, the CPU baselines, the oracle check of --workload memlimit and, with the
+default workload (the 1M-atom LJ fluid), complete records under "secondary" of the metric's other configurations
+that fit one GPU: 6mrr with PME (BASELINE.json configs[2]) and the 256k-atom LJ fluid (configs[1]).  At N > 1 the
+record carries its roofline either way.
 """
 import argparse
 import json
@@ -215,7 +220,8 @@ def measure_traffic(workload, timeout_s=90):
     spec = importlib.util.spec_from_file_location("mhip_summarize", os.path.join(ROOT, "profiles", "summarize.py"))
     summ = importlib.util.module_from_spec(spec); spec.loader.exec_module(summ)
     env = dict(os.environ, MOLLYHIP_BENCH_CHILD="1", TMPDIR="/tmp")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "200", "--warmup", "50", "--profile-steps", "50", "--no-cpu-baseline", "--no-secondary"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "200", "--warmup", "50", "--profile-steps", "50", "--no-cpu-baseline", "--no-secondary",
+           "--full"]
     acc = {}
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="mhip_pmc_", dir="/tmp")
@@ -245,7 +251,8 @@ def measure_traffic(workload, timeout_s=90):
 
 def run_single(m, workload, args, steps, warmup, profile_steps, outputs=None):
     """One workload on one GPU → (record, case, dtype, dt).  Timed region: exactly `steps` steps, inputs resident in HBM,
-    stream drained on both sides.  outputs (a dict): receives the state the last timed step left, as a caller reads it back."""
+    stream drained on both sides.  outputs (a dict): receives the state the last timed step left, as a caller reads it back.
+    profile_steps None: no profiling pass (a plain run; the stats then carry no stage times)."""
     L = m.lib()
     case, dtype, dt = make_case(workload)
     s = case.system(m, dtype)
@@ -278,24 +285,28 @@ def run_single(m, workload, args, steps, warmup, profile_steps, outputs=None):
         s.pull_state()
         outputs[workload + "_coords"] = s.coords.copy()
         outputs[workload + "_velocities"] = s.velocities.copy()
-    # separate pass with hipEvent stage timers on the engine's stream (never mixed into the timed region).  It follows the timed steps
-    # without a pause: a mhip_get_stats in between (an export-sized kernel + host work, tens of ms) left the GPU idle long enough for
-    # its clocks to drop, and a 200-step pass measured every kernel 6 % slow (force pass 92.8 against 87.1 µs on one box).
-    s._check(L.mhip_set_profiling(ctx, 1))
-    run(first, profile_steps)
-    st = s.stats()
-    s._check(L.mhip_set_profiling(ctx, 0))
+    extra = {"timed_window": "as scheduled"}
+    if profile_steps is None:
+        st = s.stats()
+    else:
+        # separate pass with hipEvent stage timers on the engine's stream (never mixed into the timed region).  It follows the timed steps
+        # without a pause: a mhip_get_stats in between (an export-sized kernel + host work, tens of ms) left the GPU idle long enough for
+        # its clocks to drop, and a 200-step pass measured every kernel 6 % slow (force pass 92.8 against 87.1 µs on one box).
+        s._check(L.mhip_set_profiling(ctx, 1))
+        run(first, profile_steps)
+        st = s.stats()
+        s._check(L.mhip_set_profiling(ctx, 0))
+        extra["list_upkeep_in_profile_pass"] = {"outer_searches": st["prof_calls"][1], "prunes": st["prof_calls"][4], "steps": profile_steps}   # launches counted by the stage timers
     s._check(L.mhip_check_finite(ctx))
     s.close()
-    extra = {"timed_window": "as scheduled",
-             "list_upkeep_in_profile_pass": {"outer_searches": st["prof_calls"][1], "prunes": st["prof_calls"][4], "steps": profile_steps}}   # launches counted by the stage timers
     return ms_per_step, st, extra, case, dtype, dt
 
 
 def run_force_calls(m, workload, args, outputs=None):
     """The reference's own GPU benchmark shape (benchmark/benchmark_gpu_tiles.jl:103-165): the median wall time of one forces! call and of
     one potential_energy call — each drained — with a step counter that advances by one per call, so that every tenth call is a rebuild step
-    of the GPU neighbour finder.  --steps = the samples (the reference: 10).  One record per case (dense, sparse)."""
+    of the GPU neighbour finder.  --steps = the samples (the reference: 10).  One record per case (dense, sparse); the kernel's stage-timed pass
+    (roofline) and the CPU leg with --full only."""
     import ctypes as C
     import importlib
     import torch
@@ -321,18 +332,21 @@ def run_force_calls(m, workload, args, outputs=None):
         if outputs is not None:      # the forces of the last timed forces call and the energy of the last timed energy call
             outputs[name + "_forces"] = f.cpu().numpy()
             outputs[name + "_potential_energy"] = np.array([pe.value], dtype=np.float64)
-        s._check(L.mhip_set_profiling(ctx, 1))
-        for k in range(args.steps, args.steps + 50):
-            forces(k)
+        if args.full:      # 50 more forces calls with the stage timers on: the kernel's own time
+            s._check(L.mhip_set_profiling(ctx, 1))
+            for k in range(args.steps, args.steps + 50):
+                forces(k)
         st = s.stats()
-        s._check(L.mhip_set_profiling(ctx, 0))
-        kern_ms = st["prof_ms"][0] / max(st["prof_calls"][0], 1)
         rec = {"case": name, "box_nm": float(case.box[0]), "n_atoms": case.n, "forces_call_ms_median": float(np.median(tf)), "forces_call_ms_min": float(min(tf)),
                "potential_energy_call_ms_median": float(np.median(te)), "samples": args.steps,
-               "pairs_half_list": st["n_pairs_full"] // 2, "k_forces_us": kern_ms * 1e3, "force_pass_bytes": st["force_pass_bytes"],
-               "roofline_frac": (st["force_pass_bytes"] / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if kern_ms > 0 else None,
+               "pairs_half_list": st["n_pairs_full"] // 2, "force_pass_bytes": st["force_pass_bytes"],
                "rebuilds": st["n_rebuilds"], "block_atoms": st["block_atoms"], "j_split": st["j_split"]}
-        if not args.no_cpu_baseline:      # the oracle's forces over its own list, all cores (the reference's forces! minus the neighbour search)
+        if args.full:
+            s._check(L.mhip_set_profiling(ctx, 0))
+            kern_ms = st["prof_ms"][0] / max(st["prof_calls"][0], 1)
+            rec["k_forces_us"] = kern_ms * 1e3
+            rec["roofline_frac"] = (st["force_pass_bytes"] / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if kern_ms > 0 else None
+        if args.full and not args.no_cpu_baseline:      # the oracle's forces over its own list, all cores (the reference's forces! minus the neighbour search)
             orc = native_oracle()
             o = orc.from_case(case, np.float32); o.native = True
             nt = min(os.cpu_count() or 1, 64)
@@ -345,14 +359,16 @@ def run_force_calls(m, workload, args, outputs=None):
         s.close()
         out.append(rec)
     d = out[0]
-    return {"metric": "forces_call_ms_median", "value": d["forces_call_ms_median"], "unit": "ms", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+    line = {"metric": "forces_call_ms_median", "value": d["forces_call_ms_median"], "unit": "ms", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": d["forces_call_ms_median"], "higher_is_better": False, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": WORKLOADS[workload], "name": workload, "n_atoms": 4096, "parallelism": "single domain", "timed_window": "median of --steps drained calls"},
-            "roofline": {"bound": "hbm", "kernel": "k_forces", "achieved": d["force_pass_bytes"] / (d["k_forces_us"] * 1e-6) / 1e9 if d["k_forces_us"] else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": d["roofline_frac"], "traffic": None, "algorithmic_bytes_per_launch": d["force_pass_bytes"], "avg_launch_ms": d["k_forces_us"] * 1e-3},
-            "cpu_baseline": ({"value": d["cpu_forces_call_ms"], "unit": "ms per forces call", "cores": d["cpu_cores"], "kind": "port",
-                              "sample": "5 calls of the oracle's threaded pair loop over its own neighbour list, same system"} if "cpu_forces_call_ms" in d else None),
-            "cases": out}
+            "config": {"workload": WORKLOADS[workload], "name": workload, "n_atoms": 4096, "parallelism": "single domain", "timed_window": "median of --steps drained calls"}}
+    if args.full:
+        line["roofline"] = {"bound": "hbm", "kernel": "k_forces", "achieved": d["force_pass_bytes"] / (d["k_forces_us"] * 1e-6) / 1e9 if d["k_forces_us"] else None, "peak": HBM_PEAK_GBS,
+                            "unit": "GB/s", "frac": d["roofline_frac"], "traffic": None, "algorithmic_bytes_per_launch": d["force_pass_bytes"], "avg_launch_ms": d["k_forces_us"] * 1e-3}
+    line["cpu_baseline"] = ({"value": d["cpu_forces_call_ms"], "unit": "ms per forces call", "cores": d["cpu_cores"], "kind": "port",
+                             "sample": "5 calls of the oracle's threaded pair loop over its own neighbour list, same system"} if "cpu_forces_call_ms" in d else None)
+    line["cases"] = out
+    return line
 
 
 def memlimit_trial(m, n, check=False, seed=7):
@@ -478,12 +494,12 @@ def memlimit_oracle_check(W, x, f, box, n_inner=100_000):
 
 def run_memlimit(m, args):
     """docs/src/examples.md:969-1017 on this GPU: the atom count doubled from --memlimit-start until a size fails, then four bisection steps between the last size that
-    ran and the first that did not.  The reference's published results: 60 000 (RTX 2080 Ti, 11 GB), 140 000 (RTX A6000, 48 GB), 120 000 (RTX 5090, 32 GB)."""
+    ran and the first that did not; with --full the first size is also checked against the oracle.  The reference's published results: 60 000 (RTX 2080 Ti, 11 GB), 140 000 (RTX A6000, 48 GB), 120 000 (RTX 5090, 32 GB)."""
     trials = []
     n = args.memlimit_start
     best, fail = None, None
     while True:
-        r = memlimit_trial(m, n, check=(n == args.memlimit_start))
+        r = memlimit_trial(m, n, check=(args.full and n == args.memlimit_start))
         trials.append(r)
         print(f"[memlimit] {n} atoms: {'ok' if r['ok'] else 'FAILED'} {r.get('ms_per_step', '')} ms/step, {r.get('hbm_in_use_gb', '')} GB {r.get('error', '')}", file=sys.stderr)
         if not r["ok"]:
@@ -516,10 +532,9 @@ def run_memlimit(m, args):
             "reference_published": {"NVIDIA GeForce RTX 2080 Ti (11 GB)": 60000, "NVIDIA RTX A6000 (48 GB)": 140000, "NVIDIA GeForce RTX 5090 (32 GB)": 120000}}
 
 
-def make_record(workload, case, dtype, dt, ms_per_step, st, extra, world, args, steps, warmup, profile_steps, live=None):
-    steps_s = 1e3 / ms_per_step
-    ns_day = steps_s * (dt * 1e3) * 86400 * 1e-6        # dt [ps] → fs
-    n_atoms = case.n
+def roofline_record(workload, dtype, n_atoms, ms_per_step, st, profile_steps, ids, live=None):
+    """the record's `roofline`: the pair pass and the two list-upkeep kernels, timed by the stage timers of the profiling pass (--full).
+    ids = (lib_build_id, kernel_src_id) of this run."""
     force_ms = st["prof_ms"][0] / max(st["prof_calls"][0], 1)
     # the large one-type fluids run the plain pair pass with the integrator in its epilogue (k_forces STEP: no force array, no integrator launch).  Such a launch
     # is priced by SURVEY §8(d)'s model — every per-atom array touched once per pass — applied to what it does: the force pass's N(R_p + 3w) + 4L without the
@@ -530,7 +545,7 @@ def make_record(workload, case, dtype, dt, ms_per_step, st, extra, world, args, 
     fbytes = st["force_pass_bytes"] + 9 * w_bytes * n_atoms if fused else st["force_pass_bytes"]
     achieved = fbytes / (force_ms * 1e-3) / 1e9 if force_ms > 0 else None
     traffic, traffic_src, traffic_id = load_traffic(workload)
-    build_id, src_id = lib_build_id(), kernel_src_id()
+    build_id, src_id = ids
     live = live or {}
     if "plain" in live:      # measured in this run (measure_traffic): the library's own ids
         traffic, traffic_src, traffic_id = live["plain"]["bytes"], None, (build_id, src_id)
@@ -570,6 +585,15 @@ def make_record(workload, case, dtype, dt, ms_per_step, st, extra, world, args, 
                 "list_upkeep": {"prune": upkeep("_prune", 4, st.get("prune_pass_bytes", 0), "k_forces<PRUNE> (+ k_prune_summary)"),
                                 "build": upkeep("_build", 1, st.get("build_pass_bytes", 0), "k_build (+ k_build_summary)"),
                                 "ms_per_step": per_step(1) + per_step(4) + per_step(3)}}
+    return roofline
+
+
+def make_record(workload, case, dtype, dt, ms_per_step, st, extra, world, args, steps, warmup, profile_steps, live=None):
+    """profile_steps None: a plain run, whose stats carry no stage times — the record has no `roofline`."""
+    steps_s = 1e3 / ms_per_step
+    ns_day = steps_s * (dt * 1e3) * 86400 * 1e-6        # dt [ps] → fs
+    n_atoms = case.n
+    build_id, src_id = lib_build_id(), kernel_src_id()
     line = {
         "metric": "ns_per_day", "value": ns_day, "unit": "ns/day", "n_gpus": world, "steps": steps, "warmup": warmup,
         "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -582,10 +606,11 @@ def make_record(workload, case, dtype, dt, ms_per_step, st, extra, world, args, 
                    "parallelism": "single domain" if world == 1 else extra.get("parallelism"),
                    "block_atoms": st["block_atoms"], "j_split": st["j_split"], "pairs_half_list": st["n_pairs_full"] // 2,
                    "timed_window": extra.get("timed_window", "as scheduled")},
-        "roofline": roofline,
-        "engine": {k: st[k] for k in ("n_blocks", "block_atoms", "j_split", "max_tile_atoms", "tile_atoms_total", "lds_bytes",
-                                      "n_list_slots", "n_pairs_full", "minimg_mode", "n_rebuilds", "n_outer_builds", "n_filter_passes", "last_rebuild_ms")},
     }
+    if profile_steps is not None:
+        line["roofline"] = roofline_record(workload, dtype, n_atoms, ms_per_step, st, profile_steps, (build_id, src_id), live)
+    line["engine"] = {k: st[k] for k in ("n_blocks", "block_atoms", "j_split", "max_tile_atoms", "tile_atoms_total", "lds_bytes",
+                                         "n_list_slots", "n_pairs_full", "minimg_mode", "n_rebuilds", "n_outer_builds", "n_filter_passes", "last_rebuild_ms")}
     line.update({k: v for k, v in extra.items() if k not in ("parallelism", "timed_window")})
     return line
 
@@ -612,12 +637,14 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default 2000; forces calls of argon4096: 100)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed warm-up steps before them (default 500; argon4096: 10)")
     ap.add_argument("--workload", default=os.environ.get("MOLLYHIP_BENCH_WORKLOAD", "lj1m"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the 6mrr_pme and lj256k records that the default single-GPU run appends")
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline too: the profiling pass and roofline, the rocprofv3 traffic passes, the CPU baselines, "
+                                                         "the default workload's secondary records, memlimit's oracle check (single GPU; N > 1 always profiles)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the 6mrr_pme and lj256k records that it appends to the default workload's")
     ap.add_argument("--integrator", default="vv", choices=["vv", "langevin"], help="vv = the headline VelocityVerlet step; langevin = Langevin middle integrator (single GPU)")
-    ap.add_argument("--profile-steps", type=int, default=200, help="steps of the separate hipEvent-timed pass")
+    ap.add_argument("--profile-steps", type=int, default=200, help="steps of the separate hipEvent-timed pass (--full, or N > 1)")
     ap.add_argument("--fail-forms", default="", help=argparse.SUPPRESS)      # tests: forms of the multi-GPU step loop ("fused", "separate launches") that the last rank gives up in the untimed part
-    ap.add_argument("--traffic", default="measure", choices=["measure", "file"], help="roofline.traffic of the main workload: two rocprofv3 PMC passes of this command in child processes (default, single GPU), or the committed files under profiles/")
+    ap.add_argument("--traffic", default="measure", choices=["measure", "file"], help="--full: roofline.traffic of the main workload from two rocprofv3 PMC passes of this command in child processes (default, single GPU), or from the committed files under profiles/")
     ap.add_argument("--block-atoms", type=int, default=0, help="launch shape of the search and pair kernels: i-atoms per workgroup (64, 128, 256; 0 = the engine's choice)")
     ap.add_argument("--j-split", type=int, default=0, help="launch shape: waves sharing one atom's list (a power of two, block_atoms * j_split <= 1024)")
     ap.add_argument("--memlimit-start", type=int, default=1_000_000, help="--workload memlimit: first atom count (doubled until a size fails)")
@@ -674,14 +701,15 @@ def main():
         os.write(json_fd, (json.dumps(line) + "\n").encode())
         return
     else:
-        ms_per_step, st, extra, case, dtype, dt = run_single(m, args.workload, args, args.steps, args.warmup, args.profile_steps, outputs)
+        profile_steps = args.profile_steps if args.full else None
+        ms_per_step, st, extra, case, dtype, dt = run_single(m, args.workload, args, args.steps, args.warmup, profile_steps, outputs)
         # the counters behind roofline.traffic, taken in THIS run (two PMC passes of the same command in child processes, ≈ 20 s each) unless switched off; a run that
         # is itself such a child, or a box without rocprofv3, reads the committed files and says so
-        live = measure_traffic(args.workload) if args.traffic == "measure" and not args.block_atoms else None
-        line = make_record(args.workload, case, dtype, dt, ms_per_step, st, extra, world, args, args.steps, args.warmup, args.profile_steps, live=live)
-        if not args.no_cpu_baseline:
+        live = measure_traffic(args.workload) if args.full and args.traffic == "measure" and not args.block_atoms else None
+        line = make_record(args.workload, case, dtype, dt, ms_per_step, st, extra, world, args, args.steps, args.warmup, profile_steps, live=live)
+        if args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(case, dtype, dt)
-        if args.workload == "lj1m" and not args.no_secondary and args.integrator == "vv":
+        if args.full and args.workload == "lj1m" and not args.no_secondary and args.integrator == "vv":
             # the metric's other single-GPU configurations (BASELINE.json: "6mrr PME fp32 and 1M-atom LJ"; configs[1] = 256k LJ): same
             # protocol, their own step counts (both run in seconds), complete records
             line["secondary"] = []

@@ -26,21 +26,23 @@ def _record(cmd, env=None, timeout=600):
     return json.loads(lines[0])
 
 
-def _check_contract(d, n_gpus, steps, warmup):
+def _check_contract(d, n_gpus, steps, warmup, roofline=True):
     assert d["metric"] == "ns_per_day" and d["unit"] == "ns/day" and d["higher_is_better"] is True
     assert d["n_gpus"] == n_gpus and d["steps"] == steps and d["warmup"] == warmup
     assert d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f32" and d["data"] == "synthetic" and d["scaling"] == "strong"
     assert d["vs_baseline"] is None
+    assert "workload" in d["config"] and "timed_window" in d["config"]
+    if not roofline:
+        return
     r = d["roofline"]
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and r["peak"] == 8000.0 and r["achieved"] > 0
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12
-    assert "workload" in d["config"] and "timed_window" in d["config"]
 
 
 def test_bench_single_gpu_record(pkg, tmp_path):
-    """--steps K times exactly K steps, and --dump-outputs writes the state the last of them left"""
-    cmd = lambda steps, out: [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "5", "--workload", "lj256k", "--equil", "300", "--no-cpu-baseline",
-                              "--traffic", "file", "--dump-outputs", str(tmp_path / out)]
+    """--steps K times exactly K steps, and --dump-outputs writes the state the last of them left (with --full: the roofline of a profiling pass beside them)"""
+    cmd = lambda steps, out: [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "5", "--workload", "lj256k", "--equil", "300", "--full",
+                              "--no-cpu-baseline", "--traffic", "file", "--dump-outputs", str(tmp_path / out)]
     d = _record(cmd(20, "a"))
     _check_contract(d, 1, 20, 5)
     assert d["config"]["parallelism"] == "single domain"
@@ -58,10 +60,25 @@ def test_bench_single_gpu_record(pkg, tmp_path):
     assert d25["steps"] == 25 and not np.array_equal(np.load(tmp_path / "b" / "lj256k_coords.npy"), x)
 
 
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` as the driver runs it (shortened equilibration): the 1M-atom record's contract and the dump of its
+    last timed step, and nothing that takes runs of its own — no profiling pass, no traffic passes, no CPU legs, no secondary configurations."""
+    d = _record([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--equil", "100", "--dump-outputs", str(tmp_path)])
+    _check_contract(d, 1, 20, 5, roofline=False)
+    assert d["config"]["name"] == "lj1m" and d["config"]["parallelism"] == "single domain" and d["config"]["timed_window"] == "as scheduled"
+    for k in ("roofline", "cpu_baseline", "secondary", "list_upkeep_in_profile_pass"):
+        assert k not in d, k
+    assert list(d.keys())[-1] == "summary" and sorted(d["summary"]) == ["lj1m_ms_per_step", "lj1m_ns_day"]
+    assert abs(d["summary"]["lj1m_ms_per_step"] - d["ms_per_step"]) < 1e-5
+    assert sorted(os.listdir(tmp_path)) == ["lj1m_coords.npy", "lj1m_velocities.npy"]
+    x, v = np.load(tmp_path / "lj1m_coords.npy"), np.load(tmp_path / "lj1m_velocities.npy")
+    assert x.shape == v.shape == (100 ** 3, 3) and x.dtype == v.dtype == np.float32 and np.isfinite(x).all() and np.isfinite(v).all()
+
+
 def test_bench_default_workload_carries_the_other_configurations():
-    """`python bench.py --gpus 1` as the driver runs it (shortened: no equilibration, no CPU legs): the 1M-atom record plus complete
+    """`python bench.py --gpus 1 --full` (shortened: no equilibration, no CPU legs): the 1M-atom record plus complete
     records of 6mrr with PME and of the 256k-atom fluid under `secondary`."""
-    d = _record([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--equil", "100", "--no-cpu-baseline", "--profile-steps", "50"])
+    d = _record([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--equil", "100", "--full", "--no-cpu-baseline", "--profile-steps", "50"])
     _check_contract(d, 1, 20, 5)
     assert d["config"]["name"] == "lj1m" and [r["config"]["name"] for r in d["secondary"]] == ["6mrr_pme", "lj256k"]
     for r in d["secondary"]:
@@ -113,9 +130,9 @@ def test_bench_two_ranks_falls_back_collectively_when_a_form_of_the_step_loop_fa
 
 
 def test_bench_memlimit_cli():
-    """`bench.py --workload memlimit` (the reference's GPU memory-limit recipe, docs/src/examples.md:969-1017) at a single size: the record's contract, the pair count
+    """`bench.py --workload memlimit --full` (the reference's GPU memory-limit recipe, docs/src/examples.md:969-1017) at a single size: the record's contract, the pair count
     on the closed form, Newton's third law over the box, the cube of 10^5 atoms against the oracle.  The full-size result is profiles/r06_memlimit_*.json."""
-    d = _record([sys.executable, "bench.py", "--workload", "memlimit", "--memlimit-start", "400000", "--memlimit-max", "500000"], timeout=400)
+    d = _record([sys.executable, "bench.py", "--workload", "memlimit", "--memlimit-start", "400000", "--memlimit-max", "500000", "--full"], timeout=400)
     assert d["metric"] == "max_atoms_100_steps" and d["unit"] == "atoms" and d["value"] == 400000 and d["n_gpus"] == 1 and d["dtype"] == "f32" and d["data"] == "synthetic"
     assert d["config"]["name"] == "memlimit" and "docs/src/examples.md:969-1017" in d["config"]["workload"]
     t = d["trials"][0]

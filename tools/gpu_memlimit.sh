@@ -1,7 +1,7 @@
 #!/bin/bash
 # the reference's GPU memory-limit recipe on the GPU box (bench.py --workload memlimit); $1 = tag, $2 = --memlimit-max (0: until a size fails)
 out=gpurun_out; mkdir -p $out; tag=${1:-r06}; max=${2:-0}
-timeout ${3:-1500} python bench.py --workload memlimit --memlimit-max $max > $out/${tag}_memlimit.json 2> $out/${tag}_memlimit.err; echo "memlimit rc $?"
+timeout ${3:-1500} python bench.py --workload memlimit --full --memlimit-max $max > $out/${tag}_memlimit.json 2> $out/${tag}_memlimit.err; echo "memlimit rc $?"
 grep memlimit $out/${tag}_memlimit.err | tail -20
 python - <<PY
 import json
