@@ -299,6 +299,23 @@ int32_t mhip_set_andersen(mhip_ctx* ctx, double kT, double prob, uint64_t seed);
 /* the raw generator on the device (known-answer tests): out4 = philox4x32_10(ctr4, key2) */
 int32_t mhip_philox4x32_10(const uint32_t* ctr4, const uint32_t* key2, uint32_t* out4);
 
+/* ---- constraints (SHAKE_RATTLE, constraints/shake.jl) ---------------------------------------------------------------------------- */
+/* dist_constraints (i, j, dist) and angle_constraints given as their three distances (i, j = centre, k, d_ij, d_jk, d_ik; constraints.jl:38-53).
+ * 0-based caller indices, host arrays, double lengths.  n_dist = n_angle = 0 removes the constraints.  Clusters are built as build_clusters does
+ * (constraints.jl:251-344): a central atom with 1, 2 or 3 distance constraints, or an angle triangle; MHIP_ERR_INVALID for an atom in two clusters,
+ * more than three constraints on one centre, a chain, a ring, a linear angle or an index out of range.  MHIP_ERR_UNSUPPORTED with ghosts or a domain
+ * plan, a TriclinicBoundary, or the Andersen coupling (mhip_set_andersen, prob > 0); the split step (mhip_vv_init / stage1 / stage2) and the halo
+ * paths refuse a constrained context.  mhip_vv_run and mhip_langevin_run then apply RATTLE after every kick and SHAKE (with the velocity correction
+ * v += Δx/dt) after every drift, in the reference's order (simulators.jl:589-620, 1155-1185).  The virials (virial9 of mhip_forces, mhip_*_virial)
+ * stay the force virials: they leave out the constraint contribution (shake.jl:205-470).  The solves run in double precision; RATTLE is one exact
+ * linear solve per cluster, so vel_tol is only checked to be positive. */
+int32_t mhip_set_constraints(mhip_ctx* ctx, int64_t n_dist, const int32_t* i, const int32_t* j, const double* dist,
+                             int64_t n_angle, const int32_t* ai, const int32_t* aj, const int32_t* ak, const double* d3,
+                             double dist_tol, double vel_tol, int32_t max_iters);
+/* out[8]: clusters of 2 / 3 / 4 atoms and angle clusters; constraints (degrees of freedom removed); the most SHAKE iterations any cluster took
+ * in the last run; the count of cluster-solves that stopped at max_iters since set; spare */
+int32_t mhip_constraint_info(mhip_ctx* ctx, int64_t* out8);
+
 /* ---- neighbour list export (bit-exact check) ------------------------------------------------ */
 /* Half list, each unordered pair once with i < j (0-based), special flag as neighbors.jl:411.
  * Pair SET equals the reference's for the same-precision arithmetic; order is unspecified.

@@ -60,6 +60,27 @@ function push_atoms!(c::HipContext, sys::System{3, <:ROCArray, T}) where T      
     c.atoms = sys.atoms
 end
 
+# SHAKE_RATTLE (constraints/shake.jl) from sys.constraints into the engine, which applies it inside mhip_vv_run / mhip_langevin_run: the central-atom clusters as their
+# distance constraints (k1 = centre), the angle clusters as (i, j = centre, k, d_ij, d_jk, d_ik) (constraints.jl:557-563).  Any other constraint algorithm
+# (LINCS) is refused rather than left out of the run.
+function push_constraints!(c::HipContext, sys::System{3, <:ROCArray, T}) where T
+    cons = values(sys.constraints)
+    isempty(cons) && return
+    length(cons) == 1 && cons[1] isa SHAKE_RATTLE || error("MollyHIPExt: constraints $(typeof.(cons)) are outside the engine's scope (one SHAKE_RATTLE only)")
+    sr = cons[1]
+    di = Int32[]; dj = Int32[]; dd = Float64[]
+    for cl in Array(sr.clusters12); push!(di, cl.k1 - 1); push!(dj, cl.k2 - 1); push!(dd, ustrip(cl.dist12)); end
+    for cl in Array(sr.clusters23), (k, d) in ((cl.k2, cl.dist12), (cl.k3, cl.dist13)); push!(di, cl.k1 - 1); push!(dj, k - 1); push!(dd, ustrip(d)); end
+    for cl in Array(sr.clusters34), (k, d) in ((cl.k2, cl.dist12), (cl.k3, cl.dist13), (cl.k4, cl.dist14)); push!(di, cl.k1 - 1); push!(dj, k - 1); push!(dd, ustrip(d)); end
+    ai = Int32[]; aj = Int32[]; ak = Int32[]; d3 = Float64[]
+    for cl in Array(sr.angle_clusters)
+        push!(ai, cl.k2 - 1); push!(aj, cl.k1 - 1); push!(ak, cl.k3 - 1); append!(d3, (ustrip(cl.dist12), ustrip(cl.dist13), ustrip(cl.dist23)))
+    end
+    check(c, ccall((:mhip_set_constraints, libmollyhip), Int32, (Ptr{Cvoid}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Int32},
+                                                                 Ptr{Float64}, Float64, Float64, Int32),
+                   c.ptr, length(di), di, dj, dd, length(ai), ai, aj, ak, d3, Float64(ustrip(sr.dist_tolerance)), Float64(ustrip(sr.vel_tolerance)), Int32(sr.max_iters)))
+end
+
 # The reference reads sys.atoms, sys.boundary, sys.pairwise_inters and the neighbour finder's exception caches at EVERY call (ext/MollyCUDAExt.jl:845-873); the
 # engine keeps them in its context, so every look-up checks that what it keeps is still what the System holds: a replaced boundary goes through mhip_set_box, a
 # replaced atoms array through mhip_set_atoms, new exception pairs through mhip_set_exceptions, a replaced interaction tuple makes a new context.
@@ -92,6 +113,7 @@ function context!(sys::System{3, <:ROCArray, T}, inters::Tuple=sys.pairwise_inte
             approx = typeof(b).parameters[end] === true                              # TriclinicBoundary{D, T, A, …}: A = approx_images
             check(c, ccall((:mhip_set_triclinic, libmollyhip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int32), c.ptr, bv, approx ? 1 : 0))
         end
+        no_list || push_constraints!(c, sys)
         lock(CONTEXTS_LOCK) do
             table[sys] = c
         end

@@ -20,6 +20,7 @@ Reference interfaces mirrored (Molly.jl v0.23.3):
 """
 import ctypes as C
 import math
+import warnings
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -285,6 +286,46 @@ class Langevin:
         self.noise_scale = float(np.sqrt(1.0 - self.vel_scale ** 2))
 
 
+@dataclass
+class DistanceConstraint:
+    """DistanceConstraint(i, j, dist) (constraints.jl:7-18): atoms i and j (0-based) held at distance dist (nm)"""
+    i: int
+    j: int
+    dist: float
+
+
+class AngleConstraint:
+    """AngleConstraint(i, j, k, angle_ijk, dist_ij, dist_jk) (constraints.jl:38-53): a rigid triangle around the central atom j, held as its three
+    distances; dist_ik follows from the law of cosines.  A linear angle cannot be constrained."""
+
+    def __init__(self, i, j, k, angle_ijk, dist_ij, dist_jk):
+        c = math.cos(angle_ijk)
+        if c == -1:
+            raise ValueError(f"disallowed linear angle constraint found between atoms {i}/{j}/{k}")
+        self.i, self.j, self.k = int(i), int(j), int(k)
+        self.dist_ij, self.dist_jk = float(dist_ij), float(dist_jk)
+        self.dist_ik = math.sqrt(dist_ij ** 2 + dist_jk ** 2 - 2 * dist_ij * dist_jk * c)
+
+
+class SHAKE_RATTLE:
+    """SHAKE_RATTLE(; n_atoms, dist_tolerance=1e-8 nm, vel_tolerance=1e-8 nm² ps⁻¹, dist_constraints, angle_constraints, max_iters=25) (shake.jl:6-96).
+    The clusters are built, checked and run by the engine (mhip_set_constraints): RATTLE after every kick, SHAKE after every drift."""
+
+    def __init__(self, n_atoms, dist_tolerance=1e-8, vel_tolerance=1e-8, dist_constraints=None, angle_constraints=None, max_iters=25):
+        if not dist_tolerance > 0:
+            raise ValueError("dist_tolerance must be greater than zero")
+        if not vel_tolerance > 0:
+            raise ValueError("vel_tolerance must be greater than zero")
+        self.n_atoms = int(n_atoms)
+        self.dist_tolerance, self.vel_tolerance, self.max_iters = float(dist_tolerance), float(vel_tolerance), int(max_iters)
+        self.dist_constraints = list(dist_constraints or ())
+        self.angle_constraints = list(angle_constraints or ())
+
+    @property
+    def n_constraints(self):
+        return len(self.dist_constraints) + 3 * len(self.angle_constraints)     # n_dof_lost (constraints.jl:358-372)
+
+
 def _rng(rng):
     return rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
 
@@ -300,7 +341,7 @@ class System:
 
     def __init__(self, atoms=None, coords=None, boundary=None, velocities=None, pairwise_inters=(),
                  specific_inter_lists=(), neighbor_finder=None, dtype=np.float32, device_id=0,
-                 charge=None, sigma=None, eps=None, mass=None, general_inters=(), lam=None):
+                 charge=None, sigma=None, eps=None, mass=None, general_inters=(), lam=None, constraints=()):
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
             raise ValueError("dtype must be float32 or float64")
@@ -330,6 +371,12 @@ class System:
         self.general_inters = tuple(general_inters)
         self.neighbor_finder = neighbor_finder if neighbor_finder is not None else NoNeighborFinder()
         self.device_id = device_id
+        self.constraints = tuple(constraints)
+        for c in self.constraints:
+            if not isinstance(c, SHAKE_RATTLE):
+                raise MollyHipError(-6, f"constraint algorithm {type(c).__name__} is outside the hot-path scope")
+        if len(self.constraints) > 1:
+            raise MollyHipError(-6, "one SHAKE_RATTLE per System")
         self.total_mass = float(self.masses.sum(dtype=np.float64))
         self._pushed_atoms = False
 
@@ -469,6 +516,30 @@ class System:
                 self._check(L.mhip_set_pme(self._ctx, gi.order, mesh, gi.α, gi.ϵr))
             else:
                 raise MollyHipError(-6, f"general interaction {type(gi).__name__} is outside the hot-path scope")
+        for sr in self.constraints:
+            dc, ac = sr.dist_constraints, sr.angle_constraints
+            ci, cj = i32([c.i for c in dc]), i32([c.j for c in dc])
+            cd = np.ascontiguousarray([c.dist for c in dc], dtype=np.float64)
+            ai, aj, ak = i32([c.i for c in ac]), i32([c.j for c in ac]), i32([c.k for c in ac])
+            d3 = np.ascontiguousarray([(c.dist_ij, c.dist_jk, c.dist_ik) for c in ac], dtype=np.float64).reshape(-1)
+            self._check(L.mhip_set_constraints(self._ctx, len(ci), *map(self._ptr, (ci, cj, cd)), len(ai), *map(self._ptr, (ai, aj, ak, d3)),
+                                               sr.dist_tolerance, sr.vel_tolerance, sr.max_iters))
+
+    @property
+    def n_constraints(self):
+        return sum(c.n_constraints for c in self.constraints)
+
+    def constraint_info(self):
+        """mhip_constraint_info: clusters of 2 / 3 / 4 atoms, angle clusters, constraints, the most SHAKE iterations of the last run,
+        cluster-solves stopped at max_iters since the constraints were set"""
+        out = (C.c_int64 * 8)()
+        self._check(_lib.lib().mhip_constraint_info(self.engine(), C.byref(out)))
+        keys = ("clusters12", "clusters23", "clusters34", "angle_clusters", "n_constraints", "max_iters_last_run", "n_not_converged")
+        return dict(zip(keys, list(out)[:7]))
+
+    def _refuse_constrained(self, what):
+        if self.constraints:
+            raise MollyHipError(-6, f"{what} of a constrained System is not supported (the rigid-molecule treatment stays in Julia)")
 
     def push_state(self, velocities=True):
         L = _lib.lib()
@@ -515,6 +586,7 @@ def forces(sys, step_n=0, pairwise=True, specific=True, general=True):
 def virial(sys, step_n=0, pairwise=True, specific=True, general=True):
     """virial(sys): 3×3 tensor Σ r ⊗ f of the pairwise (over the neighbour pairs, force.jl:848-852), specific (force.jl:991-1060) and
     general (PME reciprocal space, ewald.jl:701-723, 925-927) interactions (energy.jl:116-131)."""
+    sys._refuse_constrained("virial")
     L = _lib.lib()
     sys.push_state(velocities=False)
     v = np.zeros(9, np.float64)
@@ -573,8 +645,8 @@ def kinetic_energy(sys):
 
 
 def temperature(sys):
-    """T = 2 KE / (df k), df = 3N − 3 for a fully periodic box (energy.jl:158-175)."""
-    return 2 * kinetic_energy(sys) / ((3 * len(sys) - 3) * BOLTZMANN)
+    """T = 2 KE / (df k), df = 3N − 3 − n_constraints for a fully periodic box (energy.jl:158-175, constraints.jl:358-380)."""
+    return 2 * kinetic_energy(sys) / ((3 * len(sys) - 3 - sys.n_constraints) * BOLTZMANN)
 
 
 def total_energy(sys):
@@ -656,6 +728,7 @@ def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
     example: Langevin + MonteCarloBarostat).  Coordinates and velocities come back when the call returns.  rng: a numpy Generator or a seed; as in the
     reference it supplies the Philox key / counter words and the barostat's uniform numbers."""
     if isinstance(sim, SteepestDescentMinimizer):
+        sys._refuse_constrained("minimization")
         if init_step < 0:
             raise ValueError("init_step must be non-negative")
         return _minimize(sys, sim, init_step)
@@ -674,6 +747,10 @@ def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
             raise MollyHipError(-6, f"coupling {type(c).__name__} is outside the hot-path scope")
     if init_step < 0:   # check_simulate_inputs
         raise ValueError("init_step must be non-negative")
+    if barostat is not None:
+        sys._refuse_constrained("MonteCarloBarostat coupling")
+    if thermostat is not None and sys.constraints:
+        raise MollyHipError(-6, "AndersenThermostat coupling of a constrained System is not supported")
     L = _lib.lib()
     rng = _rng(rng)
     sys.push_state(velocities=True)
@@ -700,6 +777,10 @@ def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
             sys._check(L.mhip_set_andersen(sys._ctx, 0.0, 0.0, 0))
     if check_nans:
         sys._check(L.mhip_check_finite(sys._ctx))
+    if sys.constraints and sys.constraint_info()["n_not_converged"] > 0:        # shake.jl:817
+        sr = sys.constraints[0]
+        warnings.warn(f"SHAKE did not converge within {sr.max_iters} iterations for some clusters ({sys.constraint_info()['n_not_converged']} "
+                      "cluster-solves so far); consider a smaller time step or a larger max_iters")
     sys.pull_state()
     return sys
 
@@ -836,6 +917,7 @@ def _mc_attempt(sys, barostat, E, rand, n_molecules):
 def _apply_mc_barostat(sys, barostat, step_n, rng, energy=None):
     """apply_coupling!(sys, buffers, ::MonteCarloBarostat, sim, neighbors, step_n; rng) (coupling.jl:861-884).  `energy`: the potential-energy function (tests
     put the oracle's here to replay the same random numbers on the CPU)."""
+    sys._refuse_constrained("MonteCarloBarostat coupling")
     if step_n % barostat.n_steps != 0:
         return False
     energy = energy or (lambda s: potential_energy(s, step_n))

@@ -1,0 +1,394 @@
+// constraints.hip — SHAKE / RATTLE clusters and the constrained integrator launch (see constraints.h)
+#include "constraints.h"
+
+#include <algorithm>
+#include <numeric>
+
+#include "kernels.h"
+#include "philox.h"
+
+namespace mhip {
+
+// ---- host: clusters (constraints.jl:251-344) ---------------------------------------------------------------------------------------
+ClusterSet build_clusters(int64_t n_atoms, int64_t n_dist, const int32_t* ci, const int32_t* cj, const double* dist,
+                          int64_t n_angle, const int32_t* ai, const int32_t* aj, const int32_t* ak, const double* d3) {
+    auto bad = [](const std::string& m) { return ApiError{MHIP_ERR_INVALID, "constraints: " + m}; };
+    if (n_dist < 0 || n_angle < 0) throw bad("negative count");
+    if (n_dist > 0 && (!ci || !cj || !dist)) throw bad("null distance-constraint array");
+    if (n_angle > 0 && (!ai || !aj || !ak || !d3)) throw bad("null angle-constraint array");
+    auto in_range = [&](int32_t a) { return a >= 0 && (int64_t)a < n_atoms; };
+    auto length_ok = [](double d) { return d > 0 && std::isfinite(d); };
+    ClusterSet cs;
+    std::vector<int32_t> owner((size_t)n_atoms, -1);      // cluster of an atom (central-atom clusters: index of the component's root)
+    // central-atom clusters: the connected components of the distance constraints, each a star of 1..3 edges
+    std::vector<int32_t> parent((size_t)n_atoms);
+    std::iota(parent.begin(), parent.end(), 0);
+    auto find = [&](int32_t a) { while (parent[a] != a) { parent[a] = parent[parent[a]]; a = parent[a]; } return a; };
+    for (int64_t c = 0; c < n_dist; ++c) {
+        if (!in_range(ci[c]) || !in_range(cj[c])) throw bad("atom index out of range in distance constraint " + std::to_string(c));
+        if (ci[c] == cj[c]) throw bad("distance constraint " + std::to_string(c) + " joins an atom to itself");
+        if (!length_ok(dist[c])) throw bad("distance constraint " + std::to_string(c) + " has a non-positive length");
+        parent[find(ci[c])] = find(cj[c]);
+    }
+    std::vector<std::vector<int64_t>> comp_edges;
+    std::vector<int32_t> comp_of((size_t)n_atoms, -1);
+    for (int64_t c = 0; c < n_dist; ++c) {
+        const int32_t r = find(ci[c]);
+        if (comp_of[r] < 0) { comp_of[r] = (int32_t)comp_edges.size(); comp_edges.emplace_back(); }
+        comp_edges[comp_of[r]].push_back(c);
+    }
+    struct Cl { int kind; int32_t a[4]; double d[3]; };
+    std::vector<Cl> cls[4];
+    for (size_t q = 0; q < comp_edges.size(); ++q) {
+        const auto& e = comp_edges[q];
+        const std::string where = "the cluster of atom " + std::to_string(ci[e[0]]);
+        if (e.size() > 3) throw bad(where + " has " + std::to_string(e.size()) + " constraints (at most three on one central atom)");
+        int32_t centre = ci[e[0]];
+        if (e.size() > 1) {      // the atom every constraint shares
+            const int32_t c0[2] = {ci[e[0]], cj[e[0]]};
+            centre = -1;
+            for (int32_t cand : c0) {
+                bool all = true;
+                for (int64_t c : e) all = all && (ci[c] == cand || cj[c] == cand);
+                if (all) centre = cand;
+            }
+            if (centre < 0) throw bad(where + " is a chain or a ring (no central atom shared by all its constraints)");
+        }
+        Cl cl{}; cl.kind = (int)e.size() - 1; cl.a[0] = centre; cl.a[1] = cl.a[2] = cl.a[3] = -1;
+        for (size_t k = 0; k < e.size(); ++k) {
+            const int32_t other = ci[e[k]] == centre ? cj[e[k]] : ci[e[k]];
+            for (size_t m = 1; m <= k; ++m)
+                if (cl.a[m] == other) throw bad(where + " constrains the same pair twice");
+            cl.a[k + 1] = other; cl.d[k] = dist[e[k]];
+        }
+        for (size_t k = 0; k <= e.size(); ++k) owner[cl.a[k]] = (int32_t)q;
+        cls[cl.kind].push_back(cl);
+    }
+    // angle clusters: a triangle of their own, sharing no atom with any other cluster
+    for (int64_t c = 0; c < n_angle; ++c) {
+        const int32_t a[3] = {ai[c], aj[c], ak[c]};
+        const double* d = d3 + 3 * c;
+        for (int32_t x : a)
+            if (!in_range(x)) throw bad("atom index out of range in angle constraint " + std::to_string(c));
+        if (a[0] == a[1] || a[1] == a[2] || a[0] == a[2]) throw bad("angle constraint " + std::to_string(c) + " repeats an atom");
+        for (int k = 0; k < 3; ++k)
+            if (!length_ok(d[k])) throw bad("angle constraint " + std::to_string(c) + " has a non-positive length");
+        for (int32_t x : a)
+            if (owner[x] != -1) throw bad("atom " + std::to_string(x) + " is in two clusters (angle constraint " + std::to_string(c) + ")");
+        // d = (d_ij, d_jk, d_ik): a linear (or impossible) triangle has no rigid shape SHAKE can hold
+        const double s[3] = {d[0], d[1], d[2]};
+        const double sum = s[0] + s[1] + s[2];
+        if (std::min({s[0] + s[1] - s[2], s[1] + s[2] - s[0], s[0] + s[2] - s[1]}) <= 1e-6 * sum)
+            throw bad("angle constraint " + std::to_string(c) + " is linear");
+        for (int32_t x : a) owner[x] = -2;
+        Cl cl{}; cl.kind = CK_ANGLE; cl.a[0] = a[0]; cl.a[1] = a[1]; cl.a[2] = a[2]; cl.a[3] = -1; cl.d[0] = d[0]; cl.d[1] = d[1]; cl.d[2] = d[2];
+        cls[CK_ANGLE].push_back(cl);
+    }
+    // layout: kind by kind, each padded to a whole wave, then the free atoms
+    auto pad = [&]() { while (cs.atoms.size() % (4 * WAVE)) { cs.atoms.push_back(-1); cs.d.push_back(0); } };
+    for (int k = 0; k < 4; ++k) {
+        for (const Cl& cl : cls[k]) {
+            for (int m = 0; m < 4; ++m) cs.atoms.push_back(cl.a[m]);
+            for (int m = 0; m < 3; ++m) cs.d.push_back(k == CK_2 && m > 0 ? 0.0 : (k == CK_3 && m > 1 ? 0.0 : cl.d[m]));
+            cs.d.push_back(0);
+        }
+        pad();
+        cs.end[k] = (int32_t)(cs.atoms.size() / 4);
+        cs.n_kind[k] = (int64_t)cls[k].size();
+    }
+    for (int64_t a = 0; a < n_atoms; ++a)
+        if (owner[a] == -1) { cs.atoms.push_back((int32_t)a); cs.atoms.push_back(-1); cs.atoms.push_back(-1); cs.atoms.push_back(-1); for (int m = 0; m < 4; ++m) cs.d.push_back(0); }
+    cs.end[CK_FREE] = (int32_t)(cs.atoms.size() / 4);
+    cs.n_constraints = n_dist + 3 * n_angle;
+    return cs;
+}
+
+// ---- device --------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+template <int K> struct Shape;
+template <> struct Shape<CK_2> { static constexpr int NA = 2, NC = 1; };
+template <> struct Shape<CK_3> { static constexpr int NA = 3, NC = 2; };
+template <> struct Shape<CK_4> { static constexpr int NA = 4, NC = 3; };
+template <> struct Shape<CK_ANGLE> { static constexpr int NA = 3, NC = 3; };
+template <> struct Shape<CK_FREE> { static constexpr int NA = 1, NC = 0; };
+// constraint c joins local atoms ca → cb (r = x_cb − x_ca): the centre to its c-th partner, or the triangle (0,1), (1,2), (0,2)
+template <int K> __device__ constexpr int ca(int c) { return K == CK_ANGLE ? (c == 1 ? 1 : 0) : 0; }
+template <int K> __device__ constexpr int cb(int c) { return K == CK_ANGLE ? (c == 0 ? 1 : 2) : c + 1; }
+// ∂(x_cb − x_ca) / ∂g_e for a correction g_e·r_e/m on cb_e and −g_e·r_e/m on ca_e
+template <int K> __device__ inline double kcoef(int c, int e, const double* im) {
+    const int a = ca<K>(c), b = cb<K>(c), ae = ca<K>(e), be = cb<K>(e);
+    return (double)((b == be) - (b == ae)) * im[b] - (double)((a == be) - (a == ae)) * im[a];
+}
+__device__ inline double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+
+// x ← A⁻¹ b, n <= 3, Gaussian elimination without pivoting: RATTLE's matrix is B M⁻¹ Bᵀ of the constraint gradients (symmetric positive definite),
+// M-SHAKE's the same with one side taken at the start of the step — both diagonally dominant for the clusters build_clusters admits.  (Row swaps
+// would index the registers at run time and put the matrix in scratch memory.)
+template <int N> __device__ inline void solve(double (&A)[3][3], double (&b)[3]) {
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+#pragma unroll
+        for (int r = p + 1; r < N; ++r) {
+            const double f = A[r][p] / A[p][p];
+#pragma unroll
+            for (int c = p; c < N; ++c) A[r][c] -= f * A[p][c];
+            b[r] -= f * b[p];
+        }
+    }
+#pragma unroll
+    for (int p = N - 1; p >= 0; --p) {
+        double s = b[p];
+#pragma unroll
+        for (int c = p + 1; c < N; ++c) s -= A[p][c] * b[c];
+        b[p] = s / A[p][p];
+    }
+}
+
+template <class T> __device__ inline void rel(const typename Vec<T>::T4& a, const typename Vec<T>::T4& b, const GridP<T>& G, double* r) {
+    T dx, dy, dz;
+    min_image_exact(a.x, a.y, a.z, b.x, b.y, b.z, G, dx, dy, dz);      // vector(a, b) = b − a, nearest image
+    r[0] = dx; r[1] = dy; r[2] = dz;
+}
+
+// RATTLE (shake.jl:512-715): the velocities of the cluster with no component of any constrained pair's relative velocity along the
+// pair, one linear solve
+template <class T, int K> __device__ inline void rattle(const typename Vec<T>::T4* p, typename Vec<T>::T4* v, const double* im, const GridP<T>& G) {
+    constexpr int NA = Shape<K>::NA, NC = Shape<K>::NC;
+    double r[NC][3], A[3][3] = {}, b[3] = {};
+#pragma unroll
+    for (int c = 0; c < NC; ++c) rel<T>(p[ca<K>(c)], p[cb<K>(c)], G, r[c]);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const auto &va = v[ca<K>(c)], &vb = v[cb<K>(c)];
+        const double u[3] = {(double)vb.x - (double)va.x, (double)vb.y - (double)va.y, (double)vb.z - (double)va.z};
+        b[c] = -dot3(r[c], u);
+#pragma unroll
+        for (int e = 0; e < NC; ++e) A[c][e] = kcoef<K>(c, e, im) * dot3(r[c], r[e]);
+    }
+    solve<NC>(A, b);
+#pragma unroll
+    for (int k = 0; k < NA; ++k) {
+        double dv[3] = {0, 0, 0};
+#pragma unroll
+        for (int e = 0; e < NC; ++e) {
+            const double w = (double)((k == cb<K>(e)) - (k == ca<K>(e))) * b[e] * im[k];
+            dv[0] += w * r[e][0]; dv[1] += w * r[e][1]; dv[2] += w * r[e][2];
+        }
+        v[k].x = (T)((double)v[k].x + dv[0]); v[k].y = (T)((double)v[k].y + dv[1]); v[k].z = (T)((double)v[k].z + dv[2]);
+    }
+}
+
+// SHAKE: move the drifted positions p along the bonds of the start-of-step positions x0 until every constraint holds within tol.
+// Two atoms: the smaller root of the quadratic (shake.jl:717-755); more: M-SHAKE, Newton steps on all constraints at once.
+// Returns the iterations taken, negative when max_iters ran out first.
+template <class T, int K> __device__ inline int shake(const typename Vec<T>::T4* x0, typename Vec<T>::T4* p, const double* im, const double* dl,
+                                                      double tol, int max_iters, const GridP<T>& G) {
+    constexpr int NA = Shape<K>::NA, NC = Shape<K>::NC;
+    double r0[NC][3], q[NA][3], D[NA][3] = {}, g[NC] = {};
+#pragma unroll
+    for (int c = 0; c < NC; ++c) rel<T>(x0[ca<K>(c)], x0[cb<K>(c)], G, r0[c]);
+    q[0][0] = q[0][1] = q[0][2] = 0;
+#pragma unroll
+    for (int k = 1; k < NA; ++k) rel<T>(p[0], p[k], G, q[k]);
+    int it = 0; bool done = false;
+    for (;;) {
+        double s[NC][3], sig[3] = {};
+        done = true;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int a = ca<K>(c), b = cb<K>(c);
+            for (int x = 0; x < 3; ++x) s[c][x] = (q[b][x] + D[b][x]) - (q[a][x] + D[a][x]);
+            const double s2 = dot3(s[c], s[c]);
+            sig[c] = s2 - dl[c] * dl[c];
+            done = done && fabs(sqrt(s2) - dl[c]) <= tol;
+        }
+        if (done || it >= max_iters) break;
+        ++it;
+        if constexpr (NC == 1) {
+            const double kc = kcoef<K>(0, 0, im), a = kc * kc * dot3(r0[0], r0[0]), b = 2.0 * kc * dot3(s[0], r0[0]), c = sig[0];
+            const double disc = b * b - 4.0 * a * c;
+            g[0] += (disc >= 0 && b > 0) ? -2.0 * c / (b + sqrt(disc)) : -c / b;      // the root nearer zero; Newton if there is none
+        } else {
+            double J[3][3] = {}, rhs[3] = {};
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                rhs[c] = -sig[c];
+#pragma unroll
+                for (int e = 0; e < NC; ++e) J[c][e] = 2.0 * kcoef<K>(c, e, im) * dot3(s[c], r0[e]);
+            }
+            solve<NC>(J, rhs);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) g[c] += rhs[c];
+        }
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            D[k][0] = D[k][1] = D[k][2] = 0;
+#pragma unroll
+            for (int e = 0; e < NC; ++e) {
+                const double w = (double)((k == cb<K>(e)) - (k == ca<K>(e))) * g[e] * im[k];
+                D[k][0] += w * r0[e][0]; D[k][1] += w * r0[e][1]; D[k][2] += w * r0[e][2];
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NA; ++k) { p[k].x = (T)((double)p[k].x + D[k][0]); p[k].y = (T)((double)p[k].y + D[k][1]); p[k].z = (T)((double)p[k].z + D[k][2]); }
+    return done ? it : -it;
+}
+
+struct Acc { double px = 0, py = 0, pz = 0, m = 0; float da = 0.f, db = 0.f, v2 = 0.f; int max_it = 0; int n_fail = 0; };
+
+// one work item: the arithmetic of k_vv1 / k_vv_mid / k_langevin per atom, with RATTLE after every kick and SHAKE after every drift
+template <class T, int K, int MODE>
+__device__ inline void con_item(const ConP<T>& C, const ConStep<T>& A, const GridP<T>& G, int64_t t, const T* vc, bool sub, const T* sh, Acc& acc) {
+#pragma clang fp contract(off)
+    using T4 = typename Vec<T>::T4;
+    constexpr int NA = Shape<K>::NA, NC = Shape<K>::NC;
+    if (C.atoms[4 * t] < 0) return;      // padding of a kind's last wave
+    int32_t id[NA], sl[NA];
+    T4 p[NA], v[NA], f[NA];
+    double im[NA];
+#pragma unroll
+    for (int k = 0; k < NA; ++k) {
+        id[k] = C.atoms[4 * t + k]; sl[k] = C.inv[id[k]];
+        p[k] = A.pos[sl[k]]; v[k] = A.vel[sl[k]]; f[k] = A.frc[sl[k]];
+        if (A.fa) { const T4 ga = A.fa[sl[k]]; f[k].x += ga.x; f[k].y += ga.y; f[k].z += ga.z; }
+        if (sub) {                                                             // remove_CM_motion! of the step before, one launch late
+            v[k].x -= vc[0]; v[k].y -= vc[1]; v[k].z -= vc[2];
+            if constexpr (MODE == 1 || MODE == 2) { p[k].x = M<T>::sub(p[k].x, sh[0]); p[k].y = M<T>::sub(p[k].y, sh[1]); p[k].z = M<T>::sub(p[k].z, sh[2]); }
+        }
+        im[k] = v[k].w == T(0) ? 0.0 : 1.0 / (double)v[k].w;
+    }
+    T kx[NA], ky[NA], kz[NA];
+    if constexpr (MODE == 1 || MODE == 2) {
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            kx[k] = M<T>::mul(accel_of(f[k].x, v[k].w), A.dt2); ky[k] = M<T>::mul(accel_of(f[k].y, v[k].w), A.dt2); kz[k] = M<T>::mul(accel_of(f[k].z, v[k].w), A.dt2);
+            v[k].x = M<T>::add(v[k].x, kx[k]); v[k].y = M<T>::add(v[k].y, ky[k]); v[k].z = M<T>::add(v[k].z, kz[k]);   // simulators.jl:616
+        }
+        if constexpr (NC > 0) rattle<T, K>(p, v, im, G);                                                             // :620
+        if (A.cm_out)
+#pragma unroll
+            for (int k = 0; k < NA; ++k) { acc.px += (double)v[k].x * v[k].w; acc.py += (double)v[k].y * v[k].w; acc.pz += (double)v[k].z * v[k].w; acc.m += v[k].w; }
+    }
+    if constexpr (MODE != 2) {
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            if constexpr (MODE == 0) { v[k].x = step_add(v[k].x, accel_of(f[k].x, v[k].w), A.dt2); v[k].y = step_add(v[k].y, accel_of(f[k].y, v[k].w), A.dt2); v[k].z = step_add(v[k].z, accel_of(f[k].z, v[k].w), A.dt2); }
+            else if constexpr (MODE == 1) { v[k].x = M<T>::add(v[k].x, kx[k]); v[k].y = M<T>::add(v[k].y, ky[k]); v[k].z = M<T>::add(v[k].z, kz[k]); }   // :594
+            else { const T m1 = (v[k].w == T(0)) ? T(0) : T(1) / v[k].w; v[k].x += (f[k].x * m1) * A.S.dt; v[k].y += (f[k].y * m1) * A.S.dt; v[k].z += (f[k].z * m1) * A.S.dt; }   // :1176
+        }
+        if constexpr (NC > 0) rattle<T, K>(p, v, im, G);                                                             // :596 / :1180
+        T4 x0[NA], pu[NA];
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            x0[k] = p[k];
+            if constexpr (MODE != 3) { p[k].x = step_add(p[k].x, v[k].x, A.dt); p[k].y = step_add(p[k].y, v[k].y, A.dt); p[k].z = step_add(p[k].z, v[k].z, A.dt); }   // :602
+            else {                                                             // :1187-1192, kernels.jl:739
+                const StochP<T>& P = A.S;
+                p[k].x = fma_t(P.dt_half, v[k].x, p[k].x); p[k].y = fma_t(P.dt_half, v[k].y, p[k].y); p[k].z = fma_t(P.dt_half, v[k].z, p[k].z);
+                T z[3];
+                randn3<T>((uint64_t)id[k] + 1, P.ctr1, P.key, P.natoms, z);
+                const T ns = thermal_scale<T>(P.noise_kt, v[k].w);
+                v[k].x = fma_t(P.vel_scale, v[k].x, z[0] * ns); v[k].y = fma_t(P.vel_scale, v[k].y, z[1] * ns); v[k].z = fma_t(P.vel_scale, v[k].z, z[2] * ns);
+                p[k].x = fma_t(P.dt_half, v[k].x, p[k].x); p[k].y = fma_t(P.dt_half, v[k].y, p[k].y); p[k].z = fma_t(P.dt_half, v[k].z, p[k].z);
+            }
+            pu[k] = p[k];
+        }
+        if constexpr (NC > 0) {
+            const double dl[3] = {C.d[4 * t], C.d[4 * t + 1], C.d[4 * t + 2]};
+            const int it = shake<T, K>(x0, p, im, dl, C.tol, C.max_iters, G);                                         // :605 / :1195
+            acc.max_it = max(acc.max_it, it < 0 ? -it : it);
+            acc.n_fail += it < 0;
+            const T dt = MODE == 3 ? A.S.dt : A.dt;
+#pragma unroll
+            for (int k = 0; k < NA; ++k) {                                     // v += (x_constrained − x_unconstrained)/dt
+                v[k].x += (p[k].x - pu[k].x) / dt; v[k].y += (p[k].y - pu[k].y) / dt; v[k].z += (p[k].z - pu[k].z) / dt;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NA; ++k) wrap_point(p[k].x, p[k].y, p[k].z, G);                                          // :609 / :1201
+        if constexpr (MODE == 3)
+            if (A.cm_out)
+#pragma unroll
+                for (int k = 0; k < NA; ++k) { acc.px += (double)v[k].x * v[k].w; acc.py += (double)v[k].y * v[k].w; acc.pz += (double)v[k].z * v[k].w; acc.m += v[k].w; }
+    }
+#pragma unroll
+    for (int k = 0; k < NA; ++k) {
+        if (MODE != 2 || sub) A.pos[sl[k]] = p[k];
+        A.vel[sl[k]] = v[k];
+        if (A.trk_part) {
+            acc.v2 = fmaxf(acc.v2, (float)(v[k].x * v[k].x + v[k].y * v[k].y + v[k].z * v[k].z));
+            auto q = A.snap_a[sl[k]];
+            T ex = p[k].x - q.x, ey = p[k].y - q.y, ez = p[k].z - q.z;
+            disp_image(ex, ey, ez, G);
+            acc.da = fmaxf(acc.da, (float)(ex * ex + ey * ey + ez * ez));
+            q = A.snap_b[sl[k]];
+            ex = p[k].x - q.x; ey = p[k].y - q.y; ez = p[k].z - q.z;
+            disp_image(ex, ey, ez, G);
+            acc.db = fmaxf(acc.db, (float)(ex * ex + ey * ey + ez * ez));
+        }
+    }
+}
+
+template <class T, int MODE>
+__global__ void __launch_bounds__(CON_BLOCK) k_con_step(ConP<T> C, ConStep<T> A, GridP<T> G) {
+    T vc[3] = {T(0), T(0), T(0)};
+    const bool sub = A.vcm != nullptr || A.cm_in != nullptr;
+    if (A.cm_in) block_vcm<T>(A.cm_in, A.n_cm_in, vc);
+    else if (A.vcm) { vc[0] = A.vcm[0]; vc[1] = A.vcm[1]; vc[2] = A.vcm[2]; }
+    const T sh[3] = {M<T>::mul(vc[0], A.dt), M<T>::mul(vc[1], A.dt), M<T>::mul(vc[2], A.dt)};
+    Acc acc;
+    const int64_t n = C.end[CK_FREE], stride = (int64_t)gridDim.x * blockDim.x;      // (a multiple of the wave: a wave stays within one kind)
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += stride) {
+        if (t < C.end[CK_2]) con_item<T, CK_2, MODE>(C, A, G, t, vc, sub, sh, acc);
+        else if (t < C.end[CK_3]) con_item<T, CK_3, MODE>(C, A, G, t, vc, sub, sh, acc);
+        else if (t < C.end[CK_4]) con_item<T, CK_4, MODE>(C, A, G, t, vc, sub, sh, acc);
+        else if (t < C.end[CK_ANGLE]) con_item<T, CK_ANGLE, MODE>(C, A, G, t, vc, sub, sh, acc);
+        else con_item<T, CK_FREE, MODE>(C, A, G, t, vc, sub, sh, acc);
+    }
+    // the solver's counters: one vector atomic per wave into device words the host reads with the run's other read-backs
+    int mi = acc.max_it;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mi = max(mi, __shfl_xor(mi, o, 64));
+    int nf = acc.n_fail;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) nf += __shfl_xor(nf, o, 64);
+    if ((threadIdx.x & 63) == 0 && C.stat) {
+        if (mi > 0) atomicMax(&C.stat[1], (unsigned long long)mi);
+        if (nf > 0) atomicAdd(&C.stat[0], (unsigned long long)nf);
+    }
+    if (A.trk_part) {
+        __shared__ float sht[3][16];
+        const float da = wave_max(acc.da), db = wave_max(acc.db), v2 = wave_max(acc.v2);
+        if ((threadIdx.x & 63) == 0) { sht[0][threadIdx.x >> 6] = da; sht[1][threadIdx.x >> 6] = db; sht[2][threadIdx.x >> 6] = v2; }
+        __syncthreads();
+        if (threadIdx.x < 3) { float m = 0.f; for (int q = 0; q < (int)(blockDim.x >> 6); ++q) m = fmaxf(m, sht[threadIdx.x][q]); A.trk_part[threadIdx.x * gridDim.x + blockIdx.x] = m; }
+    }
+    if (A.cm_out) {
+        __shared__ double shm[4][4];
+        double px = acc.px, py = acc.py, pz = acc.pz, m = acc.m;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { px += __shfl_xor(px, o, 64); py += __shfl_xor(py, o, 64); pz += __shfl_xor(pz, o, 64); m += __shfl_xor(m, o, 64); }
+        const int w = threadIdx.x >> 6;
+        if ((threadIdx.x & 63) == 0) { shm[w][0] = px; shm[w][1] = py; shm[w][2] = pz; shm[w][3] = m; }
+        __syncthreads();
+        if (threadIdx.x < 4) { double a = 0; for (int q = 0; q < (int)(blockDim.x >> 6); ++q) a += shm[q][threadIdx.x]; A.cm_out[4 * (int64_t)blockIdx.x + threadIdx.x] = a; }
+    }
+}
+
+}  // namespace
+
+template <class T>
+void launch_con_step(hipStream_t s, int nb, int mode, const ConP<T>& C, const ConStep<T>& A, const GridP<T>& G) {
+    switch (mode) {
+    case 0: hipLaunchKernelGGL((k_con_step<T, 0>), dim3(nb), dim3(CON_BLOCK), 0, s, C, A, G); break;
+    case 1: hipLaunchKernelGGL((k_con_step<T, 1>), dim3(nb), dim3(CON_BLOCK), 0, s, C, A, G); break;
+    case 2: hipLaunchKernelGGL((k_con_step<T, 2>), dim3(nb), dim3(CON_BLOCK), 0, s, C, A, G); break;
+    default: hipLaunchKernelGGL((k_con_step<T, 3>), dim3(nb), dim3(CON_BLOCK), 0, s, C, A, G); break;
+    }
+}
+template void launch_con_step<float>(hipStream_t, int, int, const ConP<float>&, const ConStep<float>&, const GridP<float>&);
+template void launch_con_step<double>(hipStream_t, int, int, const ConP<double>&, const ConStep<double>&, const GridP<double>&);
+
+}  // namespace mhip

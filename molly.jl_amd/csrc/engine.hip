@@ -15,6 +15,7 @@
 
 #include "bonded.h"
 #include "stochastic.h"
+#include "constraints.h"
 #include "pme.h"
 #include "step_fused.h"
 #include "hilbert.h"
@@ -103,6 +104,9 @@ struct EngineBase {
     virtual void domain_run(int64_t, int64_t, double, int32_t, double*, int32_t, int64_t*, int32_t*, int64_t*) = 0;
     virtual void set_domain(const mhip_domain_geometry*, const int64_t*) = 0;
     virtual void domain_info(int64_t*) = 0;
+    virtual void set_constraints(int64_t, const int32_t*, const int32_t*, const double*, int64_t, const int32_t*, const int32_t*, const int32_t*, const double*, double, double, int32_t) = 0;
+    virtual void constraint_info(int64_t*) = 0;
+    virtual bool constrained() const = 0;
     virtual void domain_export(int64_t*, void*) = 0;
 };
 
@@ -309,6 +313,8 @@ template <class T> class Engine final : public EngineBase {
         if (h_prune) (void)hipHostFree(h_prune);
         if (ev_prune) (void)hipEventDestroy(ev_prune);
         if (h_red) (void)hipHostFree(h_red);
+        if (h_con) (void)hipHostFree(h_con);
+        con_atoms.release(); con_d.release(); con_stat.release();
         if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
 
@@ -1449,6 +1455,7 @@ template <class T> class Engine final : public EngineBase {
     void set_atom_counts(int64_t no, int64_t ng) override {
         if (no <= 0 || ng < 0 || no + ng > cap) throw ApiError{MHIP_ERR_INVALID, "atom counts exceed the context capacity"};
         if (ng > 0 && tri_mode) throw ApiError{MHIP_ERR_UNSUPPORTED, "TriclinicBoundary is single-domain"};
+        if (ng > 0 && con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain"};
         n_owned = no; n_ghost = ng; n_tot = no + ng;
         // new local atom set: restart from the identity order
         hipLaunchKernelGGL(k_iota2, dim3(std::min(cdiv(n_tot, 256), 1024)), dim3(256), 0, stream, n_tot, orig[cur].p, inv.p);
@@ -1699,6 +1706,7 @@ template <class T> class Engine final : public EngineBase {
         if (!(bv9[8] > 0)) throw ApiError{MHIP_ERR_INVALID, "third basis vector must have a positive z component"};
         for (int d = 0; d < 3; ++d) if (!cfg.periodic[d]) throw ApiError{MHIP_ERR_UNSUPPORTED, "TriclinicBoundary is periodic on all three axes"};
         if (n_ghost > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "TriclinicBoundary: single domain"};
+        if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints with a TriclinicBoundary are not supported"};
         if (std::fabs(bv9[0] - cfg.box[0]) > 1e-12 * bv9[0] || std::fabs(bv9[4] - cfg.box[1]) > 1e-12 * bv9[4] || std::fabs(bv9[8] - cfg.box[2]) > 1e-12 * bv9[8])
             throw ApiError{MHIP_ERR_INVALID, "the context's box must be (v1.x, v2.y, v3.z) of the triclinic basis"};
         MHIP_HIP(hipStreamSynchronize(stream));
@@ -1856,6 +1864,7 @@ template <class T> class Engine final : public EngineBase {
         fold_side_forces();
     }
     void vv_stage1(double dt) override {
+        if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no constraints: use mhip_vv_run"};
         if (!frc_valid) throw ApiError{MHIP_ERR_STATE, "vv_stage1 needs forces from vv_init / vv_stage2"};
         cur_dt = dt;
         tr("k_vv1");
@@ -1890,6 +1899,7 @@ template <class T> class Engine final : public EngineBase {
         if (due && !dual) refresh(step_n);
     }
     void vv_stage2(int64_t step_n, double dt) override {
+        if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no constraints: use mhip_vv_run"};
         stage2_cadenced(step_n, dt, false);
         MHIP_HIP(hipGetLastError());
     }
@@ -2020,6 +2030,7 @@ template <class T> class Engine final : public EngineBase {
     // flags bit 0: this step removes the centre-of-mass motion; bit 1: stop behind the second kick (the step's Σ m v goes to
     // cm_parts_dev as n_parts per-block partials for an all-reduce, nothing is packed) — at the rebuild cadence and at the end of a run
     void halo_mid(int64_t step_n, double dt, int32_t flags, double* cm_parts_dev, int32_t n_parts) override {
+        if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain, stepped by mhip_vv_run / mhip_langevin_run"};
         if (!hp_set) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_plan first"};
         const bool cm = (flags & 1) != 0, last = (flags & 2) != 0;
         if (cm && last && (!cm_parts_dev || n_parts < 1 || n_parts > 1024)) throw ApiError{MHIP_ERR_INVALID, "n_parts must be 1..1024"};
@@ -2227,6 +2238,7 @@ template <class T> class Engine final : public EngineBase {
     // step taken removes the centre-of-mass motion, cm_parts_dev holds its n_parts partials for the all-reduce over the ranks
     // (mhip_remove_cm_parts_dev), as after mhip_vv_halo_mid with the stop flag.  counters[0..2] += checks, prunes arranged, re-plans asked.
     void domain_run(int64_t first_step, int64_t n_steps, double dt, int32_t remove_cm_every, double* cm_parts_dev, int32_t n_parts, int64_t* steps_done, int32_t* reason, int64_t* counters) override {
+        if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain, stepped by mhip_vv_run / mhip_langevin_run"};
         if (!hp_set) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_plan first"};
         const bool solo = hp.n_cm_peers == 0 && hp.n_send_rows == 0;
         if (!solo && !xf.routes) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_routes first"};
@@ -2344,6 +2356,7 @@ template <class T> class Engine final : public EngineBase {
     // each, the face thresholds in T — every number formed the way the host planner forms it, so that both planners select the same atoms
     void set_domain(const mhip_domain_geometry* gm, const int64_t* gids_dev) override {
         if (!gm) { dom.ready = false; return; }
+        if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain"};
         if (caller_indexed_topology()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the in-engine re-plan moves atoms between ranks and resets the caller order: contexts with bonded terms, exception lists, special pairs or PME keep the host planner"};
         const int gx = gm->grid[0], gy = gm->grid[1], gz = gm->grid[2];
         if (gx < 1 || gy < 1 || gz < 1 || (int64_t)gx * gy * gz > XFER_MAX_RANKS) throw ApiError{MHIP_ERR_INVALID, "domain geometry: 1 .. 64 bricks"};
@@ -2561,10 +2574,13 @@ template <class T> class Engine final : public EngineBase {
         InRun guard_in_run(in_run);
         if (first_step == 0 && remove_cm_every != 0) remove_cm();                 // simulators.jl:563
         vv_init(first_step);                                                      // :564-571
-        vv_loop(first_step, n_steps, dt, remove_cm_every, nullptr, 0);
+        if (con_on) { con_run_start(); vv_loop_con(first_step, n_steps, dt, remove_cm_every); }
+        else vv_loop(first_step, n_steps, dt, remove_cm_every, nullptr, 0);
         flush_cm();
+        if (con_on) con_read_back();
         MHIP_HIP(hipGetLastError());
         MHIP_HIP(hipStreamSynchronize(stream));
+        if (con_on) con_after_run();
     }
     // the step loop of a single domain: forces of first_step are in place.  cm_parts_last (nullable): where the LAST step leaves its Σ m v partials (n_parts_last
     // blocks) instead of registering their removal with the context — mhip_domain_run on one brick, whose caller sums them over the (one) rank.
@@ -2632,6 +2648,92 @@ template <class T> class Engine final : public EngineBase {
         }
     }
 
+    // ---- SHAKE_RATTLE (constraints.h): clusters built on the host, one lane per cluster between consecutive force passes -----------------
+    ClusterSet con; DBuf<int32_t> con_atoms; DBuf<double> con_d; DBuf<unsigned long long> con_stat; unsigned long long* h_con = nullptr;
+    bool con_on = false; double con_tol = 1e-8; int32_t con_iters = 25;
+    int64_t con_last_max = 0, con_fails = 0;
+    bool constrained() const override { return con_on; }
+    void set_constraints(int64_t n_dist, const int32_t* ci, const int32_t* cj, const double* dist, int64_t n_angle, const int32_t* ai, const int32_t* aj,
+                         const int32_t* ak, const double* d3, double dist_tol, double vel_tol, int32_t max_iters) override {
+        if (n_dist == 0 && n_angle == 0) {      // removal: the context steps as one that never had constraints
+            con_on = false; con = ClusterSet{}; con_atoms.release(); con_d.release(); con_stat.release(); con_last_max = con_fails = 0;
+            return;
+        }
+        if (n_ghost > 0 || dom.ready || xf.world > 1) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain"};
+        if (tri_mode) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints with a TriclinicBoundary are not supported"};
+        if (andersen_prob > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen thermostat with constraints is not supported (a re-drawn velocity breaks RATTLE)"};
+        if (!(dist_tol > 0) || !(vel_tol > 0) || max_iters < 1) throw ApiError{MHIP_ERR_INVALID, "constraints: tolerances must be positive and max_iters at least 1"};
+        ClusterSet cs = build_clusters(cfg.n_atoms, n_dist, ci, cj, dist, n_angle, ai, aj, ak, d3);
+        MHIP_HIP(hipStreamSynchronize(stream));
+        con_atoms.reserve(cs.atoms.size()); con_d.reserve(cs.d.size()); con_stat.reserve(2);
+        MHIP_HIP(hipMemcpy(con_atoms.p, cs.atoms.data(), cs.atoms.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        MHIP_HIP(hipMemcpy(con_d.p, cs.d.data(), cs.d.size() * sizeof(double), hipMemcpyHostToDevice));
+        MHIP_HIP(hipMemset(con_stat.p, 0, 2 * sizeof(unsigned long long)));
+        if (!h_con) MHIP_HIP(hipHostMalloc((void**)&h_con, 2 * sizeof(unsigned long long)));
+        h_con[0] = h_con[1] = 0;
+        con = std::move(cs); con_tol = dist_tol; con_iters = max_iters; con_on = true; con_last_max = con_fails = 0;
+    }
+    // clusters of 2 / 3 / 4 atoms, angle clusters, constraints, the most SHAKE iterations of the last run, solves stopped at max_iters since set, spare
+    void constraint_info(int64_t* out8) override {
+        out8[0] = con.n_kind[0]; out8[1] = con.n_kind[1]; out8[2] = con.n_kind[2]; out8[3] = con.n_kind[3];
+        out8[4] = con_on ? con.n_constraints : 0; out8[5] = con_last_max; out8[6] = con_fails; out8[7] = 0;
+    }
+    int con_blocks() const { return std::max(1, std::min(cdiv(con.end[CK_FREE], CON_BLOCK), 1024)); }      // (<= 1024: the Σ m v partials fit a half of cm_step)
+    void con_run_start() { MHIP_HIP(hipMemsetAsync(con_stat.p + 1, 0, sizeof(unsigned long long), stream)); }
+    // the solver's counters travel with the run's closing synchronisation: no read-back inside the step loop
+    void con_read_back() { MHIP_HIP(hipMemcpyAsync(h_con, con_stat.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream)); }
+    void con_after_run() { con_fails = (int64_t)h_con[0]; con_last_max = (int64_t)h_con[1]; }
+    // one k_con_step launch (mode: constraints.h) over the current order, the pending Σ m v removal in front
+    void con_launch(int mode, int nb, double dt, double* cm_out, bool measure, const StochP<T>* S) {
+        ConP<T> C{};
+        C.atoms = con_atoms.p; C.d = con_d.p; C.inv = inv.p; for (int k = 0; k < CK_N; ++k) C.end[k] = con.end[k];
+        C.tol = con_tol; C.max_iters = con_iters; C.stat = con_stat.p;
+        ConStep<T> A{};
+        A.pos = pos[cur].p; A.vel = vel[cur].p; A.frc = frc[cur].p; A.fa = pend_a;
+        A.vcm = pending_cm.vcm_arg(vcm.p); A.cm_in = pending_cm.parts_arg(); A.n_cm_in = pending_cm.n; A.cm_out = cm_out;
+        A.snap_a = measure ? (const T4*)pos_snap_in.p : nullptr; A.snap_b = measure ? (const T4*)pos_snap.p : nullptr; A.trk_part = measure ? trk_part.p : nullptr;
+        A.dt = T(dt); A.dt2 = T(dt) / T(2);
+        if (S) A.S = *S;
+        tr("k_con_step");
+        launch_con_step<T>(stream, nb, mode, C, A, G);
+        MHIP_HIP(hipGetLastError());
+    }
+    // vv_loop with constraints (simulators.jl:589-620): the first kick, RATTLE, drift and SHAKE once, then ONE k_con_step between consecutive
+    // force passes (closing kick, RATTLE, Σ m v, next kick, RATTLE, drift, SHAKE, velocity correction, wrap), the closing kick + RATTLE at the
+    // end.  No force launch integrates (they update one atom per lane and cannot see a cluster's partners).
+    void vv_loop_con(int64_t first_step, int64_t n_steps, double dt, int remove_cm_every) {
+        const int every = rebuild_every();
+        InRun guard_fused(in_vv_fused); in_vv_fused = true;      // (the list checks measured by k_con_step; Σ m v partials summed down by the pair pass)
+        const bool pre = dual;
+        const int64_t last = first_step + n_steps;
+        const int nb = con_blocks();
+        int half = 0;
+        if (n_steps > 0) {
+            prof.begin(2, stream);
+            con_launch(0, nb, dt, nullptr, false, nullptr);
+            prof.end(2, stream);
+            pending_cm.none(); frc_valid = false;
+        }
+        for (int64_t step = first_step + 1; step <= last; ++step) {
+            if (trk_issued && step > trk_step) resolve_track(step);
+            if (pre && check_due(step, every)) refresh(step);
+            const bool cm = remove_cm_every != 0 && step % remove_cm_every == 0;
+            step_forces(step);
+            if (!pre && check_due(step, every)) { fold_side_forces(); refresh(step); }
+            const bool measure_mid = step != last && async_ok() && !trk_issued && check_due(step + 1, every);
+            if (measure_mid) { trk_part.reserve(3 * (size_t)std::max(n_blocks, 1024)); trk_out.reserve(4); }
+            double* cm_out = cm ? cm_step.p + (size_t)half * 4 * 1024 : (double*)nullptr;
+            prof.begin(2, stream);
+            con_launch(step == last ? 2 : 1, nb, dt, cm_out, measure_mid, nullptr);
+            prof.end(2, stream);
+            if (measure_mid) issue_track(nb, step + 1);
+            if (step == last) frc_run_total = pend_a == nullptr;
+            pend_a = nullptr; pending_cm.none();
+            if (cm) { pending_cm.resum(cm_out, nb); half ^= 1; }
+            if (step != last) frc_valid = false;
+        }
+    }
+
     // ---- stochastic dynamics (kernels in stochastic.hip) ------------------------------------------------------
     StochP<T> stoch_params(double kT, uint64_t key, uint64_t ctr1) const {
         StochP<T> P{};
@@ -2654,7 +2756,10 @@ template <class T> class Engine final : public EngineBase {
     // AndersenThermostat as the coupling of vv_run / langevin_run: applied after every step's CM removal (simulators.jl:630, 1209);
     // the reference draws (ctr1, key) from the host rng per step — here they are the words of philox(step, 0; seed)
     double andersen_kT = 0, andersen_prob = 0; uint64_t andersen_seed = 0;
-    void set_andersen(double kT, double prob, uint64_t seed) override { andersen_kT = kT; andersen_prob = prob; andersen_seed = seed; }
+    void set_andersen(double kT, double prob, uint64_t seed) override {
+        if (prob > 0 && con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen thermostat with constraints is not supported (a re-drawn velocity breaks RATTLE)"};
+        andersen_kT = kT; andersen_prob = prob; andersen_seed = seed;
+    }
     void apply_coupling(int64_t step) {
         if (!(andersen_prob > 0)) return;
         uint32_t w[4]; philox_host((uint64_t)step, 0, andersen_seed, w);
@@ -2671,14 +2776,15 @@ template <class T> class Engine final : public EngineBase {
         const int every = rebuild_every();
         cur_dt = dt;
         InRun guard_in_run(in_run);
-        InRun guard_lang(in_lang_fused); in_lang_fused = bonded.any() && pme.on() && fuse_gcv_env;
-        InRun guard_lang_async(in_lang_async); in_lang_async = (in_lang_fused || (!bonded.any() && !pme.on() && fuse_step_env)) && !(andersen_prob > 0);
+        InRun guard_lang(in_lang_fused); in_lang_fused = bonded.any() && pme.on() && fuse_gcv_env && !con_on;     // (constraints: k_con_step updates whole clusters, no force launch integrates)
+        InRun guard_lang_async(in_lang_async); in_lang_async = (in_lang_fused || con_on || (!bonded.any() && !pme.on() && fuse_step_env)) && !(andersen_prob > 0);
         if (first_step == 0 && remove_cm_every != 0) remove_cm();                 // :1115
         start_lists(first_step);                                                  // :1116
         const double vs = std::exp(-dt * friction);                               // :1091-1092
         StochP<T> P = stoch_params(kT, key, ctr1_0);
         P.dt = T(dt); P.dt_half = T(dt) / T(2); P.vel_scale = T(vs); P.noise_kt = std::sqrt(1.0 - vs * vs) * std::sqrt(kT);
-        const int nb = std::min(cdiv(n_owned, 256), 1024);
+        const int nb = con_on ? con_blocks() : std::min(cdiv(n_owned, 256), 1024);
+        if (con_on) con_run_start();
         int half = 0;
         for (int64_t step = first_step + 1; step <= first_step + n_steps; ++step) {
             // a check measured by the update launch of step s (the coordinates x_s it made) is read at the top of step s + 2, behind a whole step of queued work — the
@@ -2689,7 +2795,7 @@ template <class T> class Engine final : public EngineBase {
             // a small system's step (bonded terms + PME): its last force launch — interpolation + bonded sums — runs the update as well (step_fused.h, k_gather_collect_vv<…, LANG>),
             // every step of the run: a Langevin step is complete in itself, there is no closing half kick to keep a launch for
             const bool measure = in_lang_async && async_ok() && !trk_issued && check_due(step, every);      // the check refresh(step) below would make with a drained stream
-            step_req.gcv = bonded.any() && pme.on(); step_req.on = !bonded.any() && !pme.on(); step_req.lang = &P; step_req.cm = cm; step_req.measure = measure; step_req.dt = dt;      // (on: the packed fp32 one-type pass runs the update in its epilogue, k_forces<…, STEP, ·, LANG>)
+            step_req.gcv = bonded.any() && pme.on() && !con_on; step_req.on = !bonded.any() && !pme.on() && !con_on; step_req.lang = &P; step_req.cm = cm; step_req.measure = measure; step_req.dt = dt;      // (on: the packed fp32 one-type pass runs the update in its epilogue, k_forces<…, STEP, ·, LANG>)
             step_done = false;
             step_forces(step);                                                    // :1173
             step_req.gcv = step_req.on = false; step_req.lang = nullptr; step_req.measure = false;
@@ -2701,6 +2807,11 @@ template <class T> class Engine final : public EngineBase {
             }
             prof.begin(2, stream);
             double* cm_out = cm ? cm_step.p + (size_t)half * 4 * 1024 : (double*)nullptr;   // the other half may still be read by this launch
+            if (con_on) {      // kick, RATTLE, half drift, O-step, half drift, SHAKE per cluster (simulators.jl:1176-1201)
+                if (measure) { trk_part.reserve(3 * (size_t)std::max(n_blocks, 1024)); trk_out.reserve(4); }
+                con_launch(3, nb, dt, cm_out, measure, &P);
+                if (measure) issue_track(nb, step);
+            } else
             launch_langevin<T>(stream, nb, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, orig[cur].p, P,
                                pending_cm.vcm_arg(vcm.p), pending_cm.parts_arg(), pending_cm.n,
                                cm_out, G, (const T4*)pend_a);      // (the side array of a small system's step is added by the update itself, as k_vv_mid does: no k_add_forces launch)
@@ -2711,8 +2822,10 @@ template <class T> class Engine final : public EngineBase {
             if (check_due(step, every)) refresh(step);                            // :1211 — the next force pass prunes the fresh outer list
         }
         flush_cm();
+        if (con_on) con_read_back();
         MHIP_HIP(hipGetLastError());
         MHIP_HIP(hipStreamSynchronize(stream));
+        if (con_on) con_after_run();
     }
 
     int64_t export_neighbors(int32_t* oi, int32_t* oj, uint8_t* osp, int64_t capacity) override { return export_list(oi, oj, osp, capacity, true); }
@@ -2899,7 +3012,13 @@ int32_t mhip_check_finite(mhip_ctx* ctx) { NEED_CTX(); return guard(ctx, [&] { c
 int32_t mhip_vv_run(mhip_ctx* ctx, int64_t first, int64_t n, double dt, int32_t cm) {
     NEED_CTX(); return guard(ctx, [&] { if (n < 0 || !(dt > 0)) throw mhip::ApiError{MHIP_ERR_INVALID, "n_steps must be >= 0 and dt > 0"}; ctx->e->vv_run(first, n, dt, cm); });
 }
-int32_t mhip_vv_init(mhip_ctx* ctx, int64_t first) { NEED_CTX(); return guard(ctx, [&] { ctx->e->vv_init(first); }); }
+int32_t mhip_vv_init(mhip_ctx* ctx, int64_t first) {
+    NEED_CTX();
+    return guard(ctx, [&] {
+        if (ctx->e->constrained()) throw mhip::ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no constraints: use mhip_vv_run"};
+        ctx->e->vv_init(first);
+    });
+}
 int32_t mhip_vv_stage1(mhip_ctx* ctx, double dt) { NEED_CTX(); return guard(ctx, [&] { ctx->e->vv_stage1(dt); }); }
 int32_t mhip_vv_stage2(mhip_ctx* ctx, int64_t step_n, double dt) { NEED_CTX(); return guard(ctx, [&] { ctx->e->vv_stage2(step_n, dt); }); }
 int32_t mhip_rebuild(mhip_ctx* ctx, int64_t step_n) { NEED_CTX(); return guard(ctx, [&] { ctx->e->rebuild_now(step_n); }); }
@@ -2986,6 +3105,11 @@ int32_t mhip_domain_run(mhip_ctx* ctx, int64_t first_step, int64_t n_steps, doub
         ctx->e->domain_run(first_step, n_steps, dt, remove_cm_every, cm_parts_dev, n_parts, steps_done, reason, counters3); });
 }
 int32_t mhip_set_domain(mhip_ctx* ctx, const mhip_domain_geometry* g, const int64_t* gids_dev) { NEED_CTX(); return guard(ctx, [&] { ctx->e->set_domain(g, gids_dev); }); }
+int32_t mhip_set_constraints(mhip_ctx* ctx, int64_t n_dist, const int32_t* i, const int32_t* j, const double* dist, int64_t n_angle, const int32_t* ai, const int32_t* aj,
+                             const int32_t* ak, const double* d3, double dist_tol, double vel_tol, int32_t max_iters) {
+    NEED_CTX(); return guard(ctx, [&] { ctx->e->set_constraints(n_dist, i, j, dist, n_angle, ai, aj, ak, d3, dist_tol, vel_tol, max_iters); });
+}
+int32_t mhip_constraint_info(mhip_ctx* ctx, int64_t* out8) { NEED_CTX(); return guard(ctx, [&] { if (!out8) throw mhip::ApiError{MHIP_ERR_INVALID, "null output"}; ctx->e->constraint_info(out8); }); }
 int32_t mhip_domain_info(mhip_ctx* ctx, int64_t* out8) { NEED_CTX(); return guard(ctx, [&] { if (!out8) throw mhip::ApiError{MHIP_ERR_INVALID, "null output"}; ctx->e->domain_info(out8); }); }
 int32_t mhip_domain_export(mhip_ctx* ctx, int64_t* gid_dev, void* par4_dev) { NEED_CTX(); return guard(ctx, [&] { ctx->e->domain_export(gid_dev, par4_dev); }); }
 int32_t mhip_vv_halo_begin(mhip_ctx* ctx, double dt, const int32_t* idx, const void* shift, int64_t n, void* out) { NEED_CTX(); return guard(ctx, [&] { ctx->e->halo_begin(dt, idx, shift, n, out); }); }

@@ -18,7 +18,7 @@ def pme_mesh(box, alpha, error_tol=0.0005):
 class Case:
     def __init__(self, coords, box, lj=None, coul=None, r_list=math.inf, rebuild_every=10, velocities=None, charge=None,
                  sigma=None, eps=None, mass=None, excluded=None, special=None, bonds=None, angles=None, torsions=None,
-                 ewald_excl=None, name="case", pme=None, triclinic=None, lam=None):
+                 ewald_excl=None, name="case", pme=None, triclinic=None, lam=None, constraints=None):
         """lj: None | dict(cutoff=(kind, rc[, ra]), weight_special=1.0)
         coul: None | dict(kind="plain"|"rf"|"ewald", cutoff=(kind, rc[, ra]) (plain), rc=…, eps_rf=78.3, tol=5e-4,
                           approx=True, weight_special=1.0)"""
@@ -34,6 +34,7 @@ class Case:
         self.bonds, self.angles, self.torsions, self.ewald_excl = bonds, angles, torsions, ewald_excl
         self.name = name
         self.triclinic = triclinic   # None | dict(basis=3x3, approx_images=True): TriclinicBoundary; `box` = the basis' diagonal
+        self.constraints = constraints   # None | dict(dist=dict(i, j, d), angle=dict(i, j, k, theta, d_ij, d_jk), dist_tolerance=…, max_iters=…): SHAKE_RATTLE
         self.pme = pme       # None | dict(order=5, error_tol=5e-4, eps_r=1.0[, mesh=(nx, ny, nz)]): general interaction PME (needs coul kind "ewald")
 
     def pme_params(self, dtype):
@@ -114,10 +115,18 @@ class Case:
             gis[-1].mesh_dims = self.pme_params(dtype)["mesh"]      # the oracle and the product always see the same mesh
         boundary = m.CubicBoundary(*self.box) if self.triclinic is None else m.TriclinicBoundary(*np.asarray(self.triclinic["basis"], dtype=np.float64).reshape(3, 3),
                                                                                                   approx_images=self.triclinic.get("approx_images", True))
+        cons = ()
+        if self.constraints is not None:
+            c = self.constraints; dc, ac = c.get("dist"), c.get("angle")
+            dcs = [m.DistanceConstraint(int(i), int(j), float(d)) for i, j, d in zip(dc["i"], dc["j"], dc["d"])] if dc is not None else []
+            acs = [m.AngleConstraint(int(i), int(j), int(k), float(t), float(a), float(b))
+                   for i, j, k, t, a, b in zip(ac["i"], ac["j"], ac["k"], ac["theta"], ac["d_ij"], ac["d_jk"])] if ac is not None else []
+            cons = (m.SHAKE_RATTLE(self.n, dist_tolerance=c.get("dist_tolerance", 1e-8), vel_tolerance=c.get("vel_tolerance", 1e-8),
+                                   dist_constraints=dcs, angle_constraints=acs, max_iters=c.get("max_iters", 25)),)
         return m.System(coords=self.coords if coords is None else coords, boundary=boundary,
                         velocities=self.velocities if velocities is None else velocities, pairwise_inters=tuple(inters),
                         specific_inter_lists=tuple(sils), neighbor_finder=nf, dtype=dtype, charge=self.charge,
-                        sigma=self.sigma, eps=self.eps, mass=self.mass, general_inters=tuple(gis), lam=self.lam)
+                        sigma=self.sigma, eps=self.eps, mass=self.mass, general_inters=tuple(gis), lam=self.lam, constraints=cons)
 
 
 # ---- SURVEY §8(d) synthetic LJ fluid (argon at 1400 kg/m³, benchmark/benchmark_gpu_tiles.jl:18-25) ------
@@ -226,10 +235,49 @@ def protein_6mrr_data(path=None):
     return _npz_cache[path]
 
 
+def constraint_topology(mass, bonds, angles, constraints=None, rigid_water=False):
+    """exchange_constraints (setup.jl:1576-1630) on flat arrays: constraints None | "hbonds" (every bond with a hydrogen, mass < 1.1), rigid_water (an O
+    bonded to exactly two H and nothing else: its H-O-H angle becomes an AngleConstraint with the angle's θ0 and the two bonds' r0).  Returns
+    (constraints dict for Case or None, bonds, angles) with the constrained bonds and angles taken out of the bonded lists."""
+    if constraints not in (None, "hbonds"):
+        raise ValueError(f"constraints={constraints!r}: only None and 'hbonds' are supported (:hangles / :allbonds are outside the engine's scope)")
+    if constraints is None and not rigid_water:
+        return None, bonds, angles
+    mass = np.asarray(mass, dtype=np.float64)
+    bi, bj, r0 = (np.asarray(bonds[k]) for k in ("i", "j", "r0"))
+    ai, aj, ak, th0 = (np.asarray(angles[k]) for k in ("i", "j", "k", "th0"))
+    is_h = mass < 1.1
+    water_o = np.zeros(len(mass), bool)
+    if rigid_water:
+        deg = np.bincount(np.concatenate([bi, bj]), minlength=len(mass))
+        nh = np.bincount(np.concatenate([bi[is_h[bj]], bj[is_h[bi]]]), minlength=len(mass))
+        water_o = (~is_h) & (deg == 2) & (nh == 2)
+    a_keep = np.ones(len(ai), bool); w = []
+    r0_of = {(min(a, b), max(a, b)): r for a, b, r in zip(bi.tolist(), bj.tolist(), r0.tolist())}
+    for q in np.nonzero(water_o[aj] & is_h[ai] & is_h[ak])[0]:
+        i, j, k = int(ai[q]), int(aj[q]), int(ak[q])
+        w.append((i, j, k, float(th0[q]), r0_of[(min(i, j), max(i, j))], r0_of[(min(j, k), max(j, k))]))
+        a_keep[q] = False
+    in_water = water_o[bi] | water_o[bj]
+    cons_b = in_water.copy()
+    dist_b = np.zeros(len(bi), bool)
+    if constraints == "hbonds":
+        dist_b = (is_h[bi] | is_h[bj]) & ~in_water
+        cons_b |= dist_b
+    b_keep = ~cons_b
+    c = dict(dist=dict(i=bi[dist_b].astype(np.int32), j=bj[dist_b].astype(np.int32), d=r0[dist_b].astype(np.float64)))
+    if w:
+        wa = np.array(w, dtype=np.float64)
+        c["angle"] = dict(i=wa[:, 0].astype(np.int32), j=wa[:, 1].astype(np.int32), k=wa[:, 2].astype(np.int32), theta=wa[:, 3], d_ij=wa[:, 4], d_jk=wa[:, 5])
+    keep = lambda dct, m: {k: np.asarray(v)[m] for k, v in dct.items()}
+    return c, keep(bonds, b_keep), keep(angles, a_keep)
+
+
 def protein_6mrr(coulomb="rf", dtype=np.float64, bonded=True, lj=True, which_bonded=("bonds", "angles", "proper", "improper"), r_list=1.2,
-                 approx_erfc=True, rebuild_every=10, pme=False, path=None):
+                 approx_erfc=True, rebuild_every=10, pme=False, path=None, constraints=None, rigid_water=False):
     """coulomb: None | "rf" (CoulombReactionField rc 1.0, ε 78.3 — OpenMM CutoffPeriodic) | "ewald" (CoulombEwald rc 1.0,
-    tol 5e-4 + EwaldExclusion list), as setup.jl:1852-1913 wires them for nonbonded_method :cutoff / :pme."""
+    tol 5e-4 + EwaldExclusion list), as setup.jl:1852-1913 wires them for nonbonded_method :cutoff / :pme.  constraints None | "hbonds" and
+    rigid_water: SHAKE_RATTLE as setup.jl:1576-1630 builds it (constraint_topology)."""
     d = protein_6mrr_data(path)
     r = lambda a: np.asarray(a, dtype=np.float64).astype(dtype).astype(np.float64)   # inputs rounded to the working precision
     coords = r(d["coords"]); box = r(d["box"])
@@ -250,6 +298,14 @@ def protein_6mrr(coulomb="rf", dtype=np.float64, bonded=True, lj=True, which_bon
             kw["torsions"] = {k: np.concatenate([d[f"{p}_{k}"] for p in parts]) for k in ("i", "j", "k", "l", "periodicity", "phase", "k0")}
         if coulomb == "ewald":
             kw["ewald_excl"] = d["ewald_excl"]
+    if constraints is not None or rigid_water:
+        b = dict(i=d["bonds_i"], j=d["bonds_j"], k=d["bonds_k"], r0=d["bonds_r0"])
+        a = dict(i=d["angles_i"], j=d["angles_j"], k=d["angles_k"], kth=d["angles_kth"], th0=d["angles_th0"])
+        kw["constraints"], b, a = constraint_topology(d["mass"], b, a, constraints, rigid_water)
+        if bonded and "bonds" in which_bonded:
+            kw["bonds"] = b
+        if bonded and "angles" in which_bonded:
+            kw["angles"] = a
     return Case(coords, box, lj=dict(cutoff=("distance", 1.0), weight_special=float(d["weight_14_lj"])) if lj else None, coul=coul,
                 r_list=r_list, rebuild_every=rebuild_every, velocities=r(d["velocities_300K"]), charge=r(d["charge"]), sigma=r(d["sigma"]),
                 eps=r(d["eps"]), mass=r(d["mass"]), excluded=d["excluded"], special=d["special"], name="6mrr",
