@@ -186,13 +186,12 @@ template <class T> class Engine final : public EngineBase {
     DBuf<uint16_t> cnt_in, cnt_outer; bool cnt_outer_valid = false;
     // the group-split pair pass of small systems (forces_gs.hip): the inner list re-dealt into GS groups per block after every prune, the
     // partial forces of groups 1 .. GS − 1 (group 0 writes the force array), and which prune the list belongs to
-    DBuf<uint2> nbr_gs; DBuf<int32_t> rows_gs; DBuf<T4> frc_parts; int64_t gs_list_id = -1; bool gs_used = false;
+    DBuf<uint2> nbr_gs; DBuf<int32_t> rows_gs; DBuf<T4> frc_parts; int64_t gs_list_id = -1;
     // A prune that could drop nothing — the inner skin has grown to the reference's own r_list − cutoff, the outer list has no margin and was searched at
     // this very step (6mrr at 0.5 fs: every rebuild) — is skipped: the outer list IS the inner list (inner_is_outer: the passes over the inner list read
     // the outer arrays), and k_regroup deals it to the groups straight away.  It was a 61 µs pass (the PRUNE variant of k_forces, 1024-lane blocks) per
     // rebuild where the group-split launch that now computes the same forces takes 25 µs, spreading and bonded terms included.
     bool inner_is_outer = false; const bool adopt_env = env_int("MOLLYHIP_ADOPT_OUTER", 1) != 0; int64_t n_adopted = 0;
-    bool fuse_spread_next = false, spread_fused = false, fuse_terms_next = false, terms_fused = false;
     const int gs_env = env_int("MOLLYHIP_GROUP_SPLIT", -1);      // 0: off; 2 / 4: groups per block; −1: automatic
     int gs_groups() const {
         if (!std::is_same<T, float>::value || ljm != LJ_DIST || !(coulm == MHIP_COUL_REACTION_FIELD || (coulm == MHIP_COUL_EWALD_DIRECT && I.approx_erfc))) return 0;
@@ -203,7 +202,8 @@ template <class T> class Engine final : public EngineBase {
         if ((int64_t)n_blocks * want > 16384) return 0;      // (forced or not: the (block, group) items are uint16 and k_gs_balance stages n_blocks·GS ints in 64 KiB of LDS)
         return want;
     }
-    DBuf<int32_t> blk_ghost, blk_ghost_in; bool ghost_flags_ok = false, ghost_flags_in_ok = false, interior_done = false;
+    DBuf<int32_t> blk_ghost, blk_ghost_in; bool ghost_flags_ok = false, ghost_flags_in_ok = false;
+    bool interior_done = false;      // halo_interior ran the blocks without ghosts: the next step_forces (halo_end, a separate call) runs the rest
     int64_t last_prune_step = 0;
     int64_t pass_step = 0;       // the MD step whose coordinates the pair pass being launched sees (recorded as the step of a prune)
     DBuf<T4> pos_snap_in;        // coordinates at the last prune (validity of the inner list: 2·displacement <= skin)
@@ -790,10 +790,12 @@ template <class T> class Engine final : public EngineBase {
     // 14 % through a different register assignment, with the same instructions: measured, dropped.)
     DBuf<float> trk_part, trk_out; float* h_trk = nullptr; hipEvent_t ev_trk = nullptr;
     bool trk_issued = false; int64_t trk_step = -1, trk_prune_id = -1, trk_outer_id = -1; double trk_prev_vmax = 0;   // (ids: the running counts of prunes / outer searches)
-    bool in_vv_fused = false;
+    bool in_vv_fused = false;      // inside the fused step loop of vv_loop (async_ok and the pair pass's Σ m v summing read it)
     bool in_lang_fused = false;      // inside mhip_langevin_run of a small system whose last force launch integrates (the pair launch's extra workgroup then sums the Σ m v partials, as inside mhip_vv_run)
     bool in_lang_async = false;      // … and whose list checks are measured by that launch (no Andersen coupling behind it: the speeds the check reads would not be the run's)
     bool async_ok() const { return (in_vv_fused || in_lang_async) && dual && n_ghost == 0 && !host_prune && inner_valid && !stale; }
+    // room for the per-block maxima of a check measured by n_parts blocks
+    void trk_reserve(int n_parts) { trk_part.reserve(3 * (size_t)std::max(n_parts, 1024)); trk_out.reserve(4); }
     // the check of `step` from the n_parts per-block maxima in trk_part: reduce, copy, event
     void issue_track(int n_parts, int64_t step) {
         if (!h_trk) MHIP_HIP(hipHostMalloc((void**)&h_trk, 4 * sizeof(float)));
@@ -838,7 +840,7 @@ template <class T> class Engine final : public EngineBase {
         const int k = (int)std::min<double>(std::floor((limit - d) / per_step), every - 1);
         return k >= 3 ? k : 0;
     }
-    bool in_run = false;
+    bool in_run = false;      // inside a run that owns its step loop (steps_within reads it, deep inside refresh)
     struct InRun { bool& f; explicit InRun(bool& b) : f(b) { f = true; } ~InRun() { f = false; } };
 
     // rebuild step of the cadence (find_neighbors at step_n % n_steps == 0): a fresh search, or — with the dual list —
@@ -954,9 +956,40 @@ template <class T> class Engine final : public EngineBase {
             break;
         }
     }
+    // What one force pass (step_forces, launch_pair_kernel) is asked to do beyond the forces; the default is a plain pass.
+    // The fused step of the large one-type fluids inside mhip_vv_run (kernels.h, k_forces STEP): a plain pair pass whose epilogue is the integrator launch — second kick
+    // of this step, first kick + drift of the next, into the other position buffer (swapped in behind the launch) — with Σ m v summed and published by the grid's first
+    // workgroup.  Carried out by launch_pair_kernel when the pass is a packed plain one; every other pass keeps pair pass + k_vv_mid.
+    struct PassReq {
+        bool step = false;                      // the fused step, if the pass is the packed one (halo: it must be)
+        bool gcv = false;                       // the same request for a small system's step, whose last force launch — interpolation + bonded sums — can integrate (step_fused.h, k_gather_collect_vv)
+        bool cm = false, measure = false;       // the fused step leaves its Σ m v partials in cm_blk | measures the check of the coordinates it makes
+        double dt = 0;
+        const StochP<T>* lang = nullptr;        // the fused step is the Langevin-middle update (mhip_langevin_run)
+        bool halo = false, halo_cm_in = false;  // the fused step of a ghosted sub-domain (halo_fused) | v_cm from cm_all[0] and the peers' rows (halo_cm_publish)
+        bool fuse_spread = false, fuse_terms = false;      // a group-split pass carries the PME charge spreading | the bonded terms (step_forces decides)
+        const double* cm_sum_in = nullptr;      // mhip_domain_run on one brick: halo_mid's Σ m v partials, summed into one by the pass
+        T4* frc = nullptr;                      // the forces go here instead of frc[cur] (energy_pass)
+    };
+    struct PassRes {
+        bool step = false; int parts = 0;       // the pass integrated, leaving `parts` per-block partials (Σ m v in cm_blk's current half, maxima in trk_part)
+        bool gs = false, spread = false, terms = false;      // a group-split pass | with the charge spreading | with the bonded terms
+        bool cm_summed = false;                 // req.cm_sum_in summed into cm_fin_buf
+    };
+    // The packed fp32 one-type loop keeps the tile as three arrays SOA_STRIDE dwords apart.  packed_kind: the passes it can run;
+    // packed_stride: the smallest stride that holds a tile of tile_max atoms + sentinel, 0 for any other loop (segmented as carve_force_lds(tile_max) left it).
+    // The one answer launch_pair_kernel and packed_step_possible go by.
+    bool packed_kind(bool energy) const {
+        return std::is_same<T, float>::value && ljm == LJ_DIST_UNIFORM && coulm == MHIP_COUL_NONE && !energy && !minimg && n_special == 0 && eshift == ESHIFT_SCALED && I.lj_c12 != T(0);
+    }
+    int packed_stride(int tile_max, bool energy) const {
+        if (!packed_kind(energy) || segmented) return 0;
+        for (int k = 0; k < 3; ++k) if (tile_max + 1 < SOA_STRIDES[k]) return SOA_STRIDES[k];
+        return 0;
+    }
     // pairwise forces of the current coordinates into frc[cur] (overwrites); energy → red_part[0..n_blocks)
-    void launch_pair_kernel(bool energy, int part = 0, bool allow_gs = false) {
-        gs_used = false;
+    PassRes launch_pair_kernel(bool energy, int part = 0, bool allow_gs = false, const PassReq& req = PassReq{}) {
+        PassRes res;
         prune_resolve(!(xf_direct && n_ghost > 0));      // figures a pruning pass left behind an event: taken if they have arrived (outside the ghosted run loop: waited for)
         ForceArgs<T> A;
         A.G = G; A.I = I; A.n_owned = n_owned; A.BI = BI; A.BI_shift = ilog2(BI); A.JS = JS; A.T_cap = T_cap; A.T_lds = tile_lds; A.R_cap = R_cap;
@@ -966,7 +999,7 @@ template <class T> class Engine final : public EngineBase {
         // dual pair list: a force pass whose inner list is stale walks the OUTER list (always a valid superset — the cutoff is
         // applied per pair) and, if it is a plain force call, prunes it into the inner list on the way
         if constexpr (std::is_same<T, float>::value) {
-            if (dual && !inner_valid && !energy && allow_gs && part == 0 && !frc_override && adopt_env && gs_groups() > 0 && cnt_outer_valid && margin_zero && !(skin_in < skin)
+            if (dual && !inner_valid && !energy && allow_gs && part == 0 && !req.frc && adopt_env && gs_groups() > 0 && cnt_outer_valid && margin_zero && !(skin_in < skin)
                 && last_outer_step == pass_step && n_ghost == 0 && !host_prune) adopt_outer_list();
         }
         const bool use_inner = dual && inner_valid;
@@ -974,7 +1007,7 @@ template <class T> class Engine final : public EngineBase {
         const int GS = gs_groups();
         // a plain pass over an inner list that has its group-split form (made right behind the prune that wrote it)
         if constexpr (std::is_same<T, float>::value) {
-            if (allow_gs && GS > 0 && use_inner && !energy && part == 0 && gs_list_id == n_filters && !frc_override) {
+            if (allow_gs && GS > 0 && use_inner && !energy && part == 0 && gs_list_id == n_filters && !req.frc) {
                 const int q_lds = (max_tile_in + GS - 1) / GS + 1;      // (max_tile_in = max_tile while the outer list stands in)
                 if (gs_lds_bytes(q_lds, BI, JS / GS) <= (size_t)MAX_LDS_BYTES / GS) {
                     frc_parts.reserve((size_t)(GS - 1) * cap);
@@ -989,10 +1022,9 @@ template <class T> class Engine final : public EngineBase {
                     last_pass_tile = max_tile_in;
                     prof.begin(0, stream);
                     tr("k_forces_gs");
-                    spread_fused = false;
-                    if (fuse_spread_next || fuse_terms_next) {      // … with the charge spreading (PME) and the bonded terms of the step as further workgroups of the same launch
+                    if (req.fuse_spread || req.fuse_terms) {      // … with the charge spreading (PME) and the bonded terms of the step as further workgroups of the same launch
                         bonded.ensure_roles(stream, cap);
-                        const bool with_spread = fuse_spread_next;
+                        const bool with_spread = req.fuse_spread;
                         const int order = with_spread ? pme.order : 5;
                         // inside vv_run: the Σ m v partials of the launch before become one partial in an extra workgroup of this launch (the step's last launch reads four words)
                         const bool gs_cm_fin = (in_vv_fused || in_lang_fused) && !energy && pending_cm.mode() == 2 && pending_cm.n > 1 && pending_cm.n <= 65536;
@@ -1003,14 +1035,13 @@ template <class T> class Engine final : public EngineBase {
                                                   reinterpret_cast<const BondedArgs<float>&>(static_cast<const BondedArgs<T>&>(bonded.slot_args(G, I, pos[cur].p, inv.p))), cdiv(bonded.n_blocks(), 4), lds, stream,
                                                   gs_cm_fin ? pending_cm.parts_arg() : (const double*)nullptr, pending_cm.n, gs_cm_fin ? cm_fin_buf.p : (double*)nullptr);
                         if (gs_cm_fin) pending_cm.moved(cm_fin_buf.p, 1);
-                        spread_fused = with_spread; terms_fused = !with_spread;
+                        res.spread = with_spread; res.terms = !with_spread;
                     } else launch_forces_gs(Z, coulm, minimg, stream);
-                    fuse_spread_next = fuse_terms_next = false;
                     prof.end(0, stream);
                     MHIP_HIP(hipGetLastError());
-                    ++n_force_calls; ++n_gs_passes; gs_used = true;
+                    ++n_force_calls; ++n_gs_passes; res.gs = true;
                     if (Z.dbg && (n_gs_passes % stamps_every()) == 0) stamps_dump("", (size_t)n_blocks * GS * 4 * 8);      // (stamp builds: tools/gs_times.py)
-                    return;
+                    return res;
                 }
             }
         }
@@ -1023,11 +1054,7 @@ template <class T> class Engine final : public EngineBase {
         A.nbr_dst = nullptr; A.rows_dst = nullptr; A.pos_snap = nullptr; A.blk_disp2 = nullptr; A.r_prune2 = r_prune2;
         A.tile_idx_dst = nullptr; A.tile_cnt_dst = nullptr; A.mark_off = 0; A.snap_dst = nullptr; A.any_special = n_special > 0 ? 1 : 0; A.eshift = eshift;
         A.cnt_dst = nullptr;
-        // the packed fp32 one-type loop keeps the tile as three arrays SOA_STRIDE dwords apart
-        const bool fast_f32 = std::is_same<T, float>::value && ljm == LJ_DIST_UNIFORM && coulm == MHIP_COUL_NONE && !energy && !minimg && !segmented && n_special == 0;
-        A.soa = 0;
-        if (fast_f32 && eshift == ESHIFT_SCALED && I.lj_c12 != T(0))
-            for (int k = 2; k >= 0; --k) if ((use_inner ? max_tile_in : max_tile) + 1 < SOA_STRIDES[k]) A.soa = SOA_STRIDES[k];   // the smallest stride that holds tile + sentinel
+        A.soa = packed_stride(use_inner ? max_tile_in : max_tile, energy);
         if (A.soa) lds_force = std::max((size_t)3 * A.soa * sizeof(float) + 64, (size_t)JS * 4 * BI * sizeof(T) + 32);   // x[], y[], z[] instead of the generic 16-byte records
         A.part = 0; A.blk_ghost = nullptr;
         if (part != 0 && !prune) {   // blocks without / with ghost atoms in their tile (flags of the tile this pass stages)
@@ -1056,51 +1083,50 @@ template <class T> class Engine final : public EngineBase {
             lds_force = (size_t)A.mark_off + prune_lds_bytes(tile_lds, BI * JS);   // + renumbering table + scan scratch + wave boxes
             if (lds_force > (size_t)MAX_LDS_BYTES) throw ApiError{MHIP_ERR_CAPACITY, "prune pass LDS carve-up exceeds 160 KiB"};
         }
-        A.blk_center = blk_center.p; A.frc = frc_override ? frc_override : frc[cur].p; A.pe_part = red_part.p;
+        A.blk_center = blk_center.p; A.frc = req.frc ? req.frc : frc[cur].p; A.pe_part = red_part.p;
         // inside vv_run: the Σ m v partials of the integrator launch before this pass become one partial here (kernels.h, cm_finalize_in_block)
         A.cm_fin_in = nullptr; A.cm_fin_n = 0; A.cm_fin_out = nullptr;
         A.vel = nullptr; A.pos_next = nullptr; A.dt = T(0); A.dt2 = T(0); A.cm_in = nullptr; A.cm_n = 0; A.cm_pub = nullptr; A.step_seq = 0; A.cm_out = nullptr; A.trk_part = nullptr; A.snap_a = nullptr; A.snap_b = nullptr;
         const bool cm_fin = (in_vv_fused || in_lang_fused) && !energy && n_ghost == 0 && part == 0 && pending_cm.mode() == 2 && pending_cm.n > 1 && pending_cm.n <= 65536;      // (the energy variants do not carry the sum)
         if (cm_fin) { cm_fin_buf.reserve(4); A.cm_fin_in = pending_cm.parts_arg(); A.cm_fin_n = pending_cm.n; A.cm_fin_out = cm_fin_buf.p; }
-        else if (cm_fin_solo_src && !energy && n_ghost == 0 && part == 0 && !cm_fin_solo_done) {      // (mhip_domain_run on one brick: halo_mid's partials)
-            cm_fin_buf.reserve(4); A.cm_fin_in = cm_fin_solo_src; A.cm_fin_n = pending_cm.n; A.cm_fin_out = cm_fin_buf.p; cm_fin_solo_done = true;
+        else if (req.cm_sum_in && !energy && n_ghost == 0 && part == 0) {      // (mhip_domain_run on one brick: halo_mid's partials)
+            cm_fin_buf.reserve(4); A.cm_fin_in = req.cm_sum_in; A.cm_fin_n = pending_cm.n; A.cm_fin_out = cm_fin_buf.p; res.cm_summed = true;
         }
         A.level_pairs = (prune && JS == 2) ? 1 : 0;      // (an atom's two sub-lists levelled before they are padded: kernels.h)
         A.dbg = (!prune && !energy) ? stamps_begin((size_t)n_blocks * 16 * 8) : nullptr;
-        // the fused step: this pass also integrates (see step_req)
-        step_done = false;
+        // the fused step: this pass also integrates (see PassReq)
         bool do_step = false;
         if constexpr (std::is_same<T, float>::value) {
-            do_step = step_req.on && fuse_step_env && fast_f32 && A.soa != 0 && use_inner && !prune && part == 0 && !frc_override && (n_ghost == 0 || halo_req.on) && pending_cm.mode() != 1;
-            if (halo_req.on && !do_step) throw ApiError{MHIP_ERR_STATE, "internal: the fused ghosted step was asked for a pass that cannot integrate"};
+            do_step = req.step && fuse_step_env && A.soa != 0 && use_inner && !prune && part == 0 && !req.frc && (n_ghost == 0 || req.halo) && pending_cm.mode() != 1;
+            if (req.halo && !do_step) throw ApiError{MHIP_ERR_STATE, "internal: the fused ghosted step was asked for a pass that cannot integrate"};
             if (do_step) {
                 pos_alt.reserve(cap); cm_blk.reserve(2 * 4 * (size_t)n_blocks + 8);
                 if (!cm_pub.p) { cm_pub.reserve(4); MHIP_HIP(hipMemsetAsync(cm_pub.p, 0, 4 * sizeof(unsigned long long), stream)); }      // (launch numbers start at 1)
-                A.vel = vel[cur].p; A.pos_next = pos_alt.p; A.dt = T(step_req.dt); A.dt2 = T(step_req.dt) / T(2);
+                A.vel = vel[cur].p; A.pos_next = pos_alt.p; A.dt = T(req.dt); A.dt2 = T(req.dt) / T(2);
                 A.cm_in = pending_cm.parts_arg(); A.cm_n = pending_cm.n; A.cm_pub = cm_pub.p; A.step_seq = ++step_seq;
-                A.cm_out = step_req.cm ? cm_blk.p + (size_t)step_half * 4 * n_blocks : (double*)nullptr;
+                A.cm_out = req.cm ? cm_blk.p + (size_t)step_half * 4 * n_blocks : (double*)nullptr;
                 A.trk_part = nullptr; A.snap_a = pos_snap_in.p; A.snap_b = pos_snap.p;
-                if (step_req.measure) { trk_part.reserve(3 * (size_t)std::max(n_blocks, 1024)); trk_out.reserve(4); A.trk_part = trk_part.p; }
+                if (req.measure) { trk_reserve(n_blocks); A.trk_part = trk_part.p; }
                 A.cm_fin_in = nullptr; A.cm_fin_n = 0; A.cm_fin_out = nullptr;      // (the head workgroup of the launch sums the partials instead)
-                if (halo_req.on) hx_fill(A);
-                if (step_req.lang) { if (halo_req.on) throw ApiError{MHIP_ERR_STATE, "internal: Langevin update asked of a ghosted step"}; A.orig = orig[cur].p; A.S = *step_req.lang; }
+                if (req.halo) hx_fill(A, req.halo_cm_in);
+                if (req.lang) { if (req.halo) throw ApiError{MHIP_ERR_STATE, "internal: Langevin update asked of a ghosted step"}; A.orig = orig[cur].p; A.S = *req.lang; }
             }
         }
         prof.begin(prune ? 4 : 0, stream);   // stage 4 = force passes that also prune the outer list
-        tr(prune ? "k_forces (prune)" : (energy ? "k_forces (energy)" : (do_step ? (halo_req.on ? "k_forces (fused ghosted step)" : "k_forces (fused step)") : "k_forces")));
+        tr(prune ? "k_forces (prune)" : (energy ? "k_forces (energy)" : (do_step ? (req.halo ? "k_forces (fused ghosted step)" : "k_forces (fused step)") : "k_forces")));
         if constexpr (std::is_same<T, float>::value) {
             if (do_step) {
-                if (halo_req.on && xf.shared_device && halo_waiter_env) {
+                if (req.halo && xf.shared_device && halo_waiter_env) {
                     // Several ranks on ONE device: the peers need the same compute units to produce what this launch would wait for, and a grid of resident,
                     // spinning workgroups can leave their kernels no room (a search kernel's 100 KB of LDS next to two spinning blocks per unit: a 2 s stall,
                     // then the time-out).  A one-workgroup launch waits instead; the pass behind it finds every word in place.
                     XferWait W{}; W.mine = reinterpret_cast<const XferHeader*>(xf.region); W.parity = (int)(xf.seq & 1u); W.seq = xf.seq; W.peers = xf.d_peers.p; W.n_peers = xf.n_peers; W.err = xf.err.p; W.ticks = xf_ticks();
                     hipLaunchKernelGGL(k_xfer_wait_all, dim3(1), dim3(64), 0, stream, W);
                 }
-                launch_forces_uniform_f32(A, false, false, lds_force, (unsigned)(BI * JS), stream, true, halo_req.on, step_req.lang != nullptr);
-                if (halo_req.on) ++xf.seq;      // (the launch's last wave announces exchange xf.seq at the peers)
+                launch_forces_uniform_f32(A, false, false, lds_force, (unsigned)(BI * JS), stream, true, req.halo, req.lang != nullptr);
+                if (req.halo) ++xf.seq;      // (the launch's last wave announces exchange xf.seq at the peers)
                 std::swap(pos[cur].p, pos_alt.p); std::swap(pos[cur].n, pos_alt.n);      // the epilogues wrote the drifted coordinates into the other buffer: it is the current one now
-                step_done = true; ++n_fused_steps; step_parts = n_blocks;
+                res.step = true; res.parts = n_blocks; ++n_fused_steps;
             } else launch_forces_any(A, energy);
         } else launch_forces_any(A, energy);
         if (cm_fin && !do_step) pending_cm.moved(cm_fin_buf.p, 1);
@@ -1147,17 +1173,14 @@ template <class T> class Engine final : public EngineBase {
                 if (debug_on) std::fprintf(stderr, "[mhip] prune: max disp %.5f nm (margin %.3f) rows %lld exceeded %d calls %lld\n", std::sqrt((double)d2), prune_margin(), (long long)total_rows, (int)prune_disp_exceeded, (long long)n_force_calls);
             }
         }
+        return res;
     }
 
     DBuf<double> cm_fin_buf;
-    const double* cm_fin_solo_src = nullptr; bool cm_fin_solo_done = false;
-    // The fused step of the large one-type fluids inside mhip_vv_run (kernels.h, k_forces STEP): a plain pair pass whose epilogue is the integrator launch — second kick
-    // of this step, first kick + drift of the next, into the other position buffer (swapped in behind the launch) — with Σ m v summed and published by the grid's first
-    // workgroup.  Asked for by vv_run (step_req), carried out by launch_pair_kernel when the pass is a packed plain one; every other pass keeps pair pass + k_vv_mid.
-    // (gcv: the same request for a small system's step, whose last force launch — interpolation + bonded sums — can integrate: step_fused.h, k_gather_collect_vv)
-    struct StepReq { bool on = false, gcv = false, cm = false, measure = false; double dt = 0; const StochP<T>* lang = nullptr; } step_req;      // (lang: gcv with the Langevin-middle update, mhip_langevin_run)
-    bool step_done = false; int step_half = 0; uint32_t step_seq = 0; int64_t n_fused_steps = 0;
-    int step_parts = 0;      // per-block partials (Σ m v in cm_blk's current half, maxima in trk_part) the fused step left behind
+    int step_half = 0;                      // the half of cm_blk the next fused step writes its Σ m v partials to (the other one is still read by that step)
+    uint32_t step_seq = 0;                  // the launch number of the last fused step: the next one publishes its Σ m v at cm_pub under one more
+    int64_t n_fused_steps = 0;              // (mhip_get_stats)
+    int step_parts = 0;                     // the per-block maxima of the last fused ghosted step (halo_fused) in trk_part: xf_issue_plan_check reduces them a step later
     const bool fuse_gcv_env = env_int("MOLLYHIP_FUSE_GATHER_VV", 1) != 0;
     DBuf<T4> pos_alt; DBuf<double> cm_blk; DBuf<unsigned long long> cm_pub;
     const bool fuse_step_env = env_int("MOLLYHIP_FUSE_STEP", 1) != 0;
@@ -1168,13 +1191,12 @@ template <class T> class Engine final : public EngineBase {
     // Would a plain pass now be the packed one-type loop over a valid inner list — the only pass that can integrate?  (launch_pair_kernel's own conditions, asked
     // BEFORE the step is put together: the domain loop leaves the unpack, integrator and pack launches out only when the pass will do their work)
     bool packed_step_possible() {
-        if constexpr (!std::is_same<T, float>::value) return false;
-        if (!fuse_step_env || !dual || !inner_valid || stale || ljm != LJ_DIST_UNIFORM || coulm != MHIP_COUL_NONE || minimg || n_special != 0 || eshift != ESHIFT_SCALED || I.lj_c12 == T(0)) return false;
+        if (!fuse_step_env || !dual || !inner_valid || stale || !packed_kind(false)) return false;
         prune_resolve(false);
         if (prune_pending && max_tile_in + 1 >= SOA_STRIDES[2]) prune_resolve(true);      // (the outer list's bound does not fit the packed loop: the pruned list's own figure is needed now)
         if (max_tile_in + 1 >= SOA_STRIDES[2]) return false;
         carve_force_lds(max_tile_in);
-        return !segmented;
+        return packed_stride(max_tile_in, false) != 0;
     }
 
     // ---- the fused step of a ghosted sub-domain (kernels.h HaloStep; tables: halo_step.h) -------------------------------------------------------------------
@@ -1185,7 +1207,6 @@ template <class T> class Engine final : public EngineBase {
         int64_t n_steps = 0;
         void release() { order.release(); flags.release(); tsrc.release(); ghost_row.release(); cm_row.release(); snd_start.release(); snd_cnt.release(); blk_send.release(); snd.release(); cm_dst.release(); ann.release(); }
     } hx;
-    struct HaloReq { bool on = false, cm_in = false; } halo_req;
     static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
     void hx_build() {
         if constexpr (std::is_same<T, float>::value) {
@@ -1228,7 +1249,7 @@ template <class T> class Engine final : public EngineBase {
             MHIP_HIP(hipGetLastError());
         }
     }
-    void hx_fill(ForceArgs<T>& A) {
+    void hx_fill(ForceArgs<T>& A, bool cm_in) {
         if constexpr (std::is_same<T, float>::value) {
             hx_build();
             HaloStep& H = A.H;
@@ -1240,7 +1261,7 @@ template <class T> class Engine final : public EngineBase {
             H.parity_send = (int)((xf.seq + 1u) & 1u); H.seq_send = xf.seq + 1u;
             H.ann = hx.ann.p; H.done = xf.done.p; H.n_done = (unsigned int)(n_blocks * (BI / WAVE));
             H.cm_row = hx.cm_row.p; H.cm_dst = hx.cm_dst.p; H.cm_rows = hp.cm_rows; H.cm_all = cm_all.p;
-            A.cm_in = halo_req.cm_in ? (const double*)cm_all.p : (const double*)nullptr;      // (a flag here: v_cm comes from cm_all[0] and the peers' rows, halo_cm_publish)
+            A.cm_in = cm_in ? (const double*)cm_all.p : (const double*)nullptr;      // (a flag here: v_cm comes from cm_all[0] and the peers' rows, halo_cm_publish)
             A.cm_n = 0;
             ++hx.n_steps;
         }
@@ -1255,13 +1276,11 @@ template <class T> class Engine final : public EngineBase {
     void halo_fused(int64_t step_n, double dt, bool cm, bool measure) {
         cur_dt = dt;
         if (check_due(step_n, rebuild_every()) && step_n != last_build_step && dual) refresh(step_n);
-        step_req.on = true; step_req.gcv = false; step_req.cm = cm; step_req.measure = measure; step_req.dt = dt;
-        halo_req.on = true; halo_req.cm_in = halo_cm_in;
-        step_done = false;
-        struct Off { StepReq& s; HaloReq& h; ~Off() { s.on = false; h.on = false; } } off{step_req, halo_req};
-        step_forces(step_n);
-        if (!step_done) throw ApiError{MHIP_ERR_STATE, "internal: the fused ghosted step did not launch"};
-        step_done = false;
+        PassReq req;
+        req.step = true; req.cm = cm; req.measure = measure; req.dt = dt; req.halo = true; req.halo_cm_in = halo_cm_in;
+        const PassRes res = step_forces(step_n, req);
+        if (!res.step) throw ApiError{MHIP_ERR_STATE, "internal: the fused ghosted step did not launch"};
+        step_parts = res.parts;
         if (cm) step_half ^= 1;
         halo_cm_in = cm; frc_valid = false; pend_a = nullptr; pending_cm.none();
         hx.trk_step = measure ? step_n + 1 : -1;
@@ -1372,56 +1391,58 @@ template <class T> class Engine final : public EngineBase {
 
     // all forces of one MD step: the pair kernel overwrites frc[cur]; the bonded terms and the PME reciprocal part ride in the same launch where the shapes
     // allow (forces_gs.hip), else follow on the same stream; a second force array a fused launch leaves behind (pend_a) is added by the consumer
-    // (second kick, or fold_side_forces)
-    void step_forces(int64_t step_n) {
+    // (second kick, or fold_side_forces).  req: see PassReq, whose fuse_* this decides.
+    PassRes step_forces(int64_t step_n, PassReq req = PassReq{}) {
         pass_step = step_n;
         if (pme.on() && n_ghost > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "PME runs on a single domain (SURVEY §8(e): 6mrr-size systems are replicas only)"};
         // (group-split passes leave partial forces that the per-atom sums of the bonded slots fold in: only where such a launch follows)
         const bool gs_ok = bonded.any() && n_ghost == 0;
         const bool small_fused = bonded.any() && pme.on() && n_ghost == 0;
         // (with the stage timers on, every job keeps its own launch: a stage's time is then that job's — bench.py's profiling pass, never its timed region)
-        fuse_spread_next = gs_ok && small_fused && pme.order >= 4 && pme.order <= 6 && !prof.on;
-        fuse_terms_next = gs_ok && !small_fused && !pme.on() && !prof.on;      // (no PME: the bonded terms alone ride with the pair groups)
-        spread_fused = terms_fused = false;
-        launch_pair_kernel(false, interior_done ? 2 : 0, gs_ok);   // (the blocks without ghosts may have run already, while the ghosts were on the wire)
-        fuse_spread_next = fuse_terms_next = false;
+        req.fuse_spread = gs_ok && small_fused && pme.order >= 4 && pme.order <= 6 && !prof.on;
+        req.fuse_terms = gs_ok && !small_fused && !pme.on() && !prof.on;      // (no PME: the bonded terms alone ride with the pair groups)
+        PassRes res = launch_pair_kernel(false, interior_done ? 2 : 0, gs_ok, req);   // (the blocks without ghosts may have run already, while the ghosts were on the wire)
         interior_done = false;
         bool redo = false;
         if (prune_disp_exceeded) {   // the outer list could not vouch for this pass: search again and redo it on the fresh list
             after_forces(step_n);
-            launch_pair_kernel(false);
+            req.fuse_spread = req.fuse_terms = false;
+            if (res.cm_summed) req.cm_sum_in = nullptr;      // (summed by the first pass)
+            const PassRes again = launch_pair_kernel(false, 0, false, req);
+            res.step = again.step; res.parts = again.parts; res.gs = again.gs; res.cm_summed |= again.cm_summed;      // (what the first pass fused in stays done)
             redo = true;
         }
-        if (gs_used) bonded.fold(frc_parts.p, gs_groups() - 1, cap);      // the next collect launch adds the groups' partial forces
+        if (res.gs) bonded.fold(frc_parts.p, gs_groups() - 1, cap);      // the next collect launch adds the groups' partial forces
         pend_a = nullptr;
         // small systems: charge spreading next to the bonded terms, force interpolation next to the bonded sums (step_fused.h)
         if (small_fused) {
             frc_side.reserve(cap);
             // … and, on a mid-run step of vv_run, the integrator in that last launch (v_cm of the step before as ONE partial, or none pending)
             GcvArgs<T> V; const GcvArgs<T>* vp = nullptr;
-            if (step_req.gcv && fuse_gcv_env && !redo && (pending_cm.mode() == 0 || (pending_cm.mode() == 2 && pending_cm.n == 1)) && pme.order >= 4 && pme.order <= 6) {
+            if (req.gcv && fuse_gcv_env && !redo && (pending_cm.mode() == 0 || (pending_cm.mode() == 2 && pending_cm.n == 1)) && pme.order >= 4 && pme.order <= 6) {
                 const int nb = (int)Pme<T>::atom_blocks(n_owned);
                 cm_blk.reserve(2 * 4 * (size_t)nb + 8);
-                if (step_req.measure) { trk_part.reserve(3 * (size_t)std::max(nb, 1024)); trk_out.reserve(4); }
+                if (req.measure) trk_reserve(nb);
                 std::memset(&V, 0, sizeof(V));
-                V.vel = vel[cur].p; V.dt = T(step_req.dt); V.dt2 = T(step_req.dt) / T(2); V.G = G;
+                V.vel = vel[cur].p; V.dt = T(req.dt); V.dt2 = T(req.dt) / T(2); V.G = G;
                 V.cm_in = pending_cm.parts_arg();
-                V.cm_out = step_req.cm ? cm_blk.p + (size_t)step_half * 4 * nb : (double*)nullptr;
-                V.snap_a = pos_snap_in.p; V.snap_b = pos_snap.p; V.trk_part = step_req.measure ? trk_part.p : (float*)nullptr;
-                if (step_req.lang) V.S = *step_req.lang;
-                vp = &V; step_parts = nb;
+                V.cm_out = req.cm ? cm_blk.p + (size_t)step_half * 4 * nb : (double*)nullptr;
+                V.snap_a = pos_snap_in.p; V.snap_b = pos_snap.p; V.trk_part = req.measure ? trk_part.p : (float*)nullptr;
+                if (req.lang) V.S = *req.lang;
+                vp = &V; res.parts = nb;
             }
             prof.begin(6, stream);
-            launch_pme_bonded_fused<T>(stream, pme, bonded, G, I, n_owned, cap, pos[cur].p, inv.p, orig[cur].p, frc[cur].p, frc_side.p, spread_fused, vp, vp && step_req.lang);
+            launch_pme_bonded_fused<T>(stream, pme, bonded, G, I, n_owned, cap, pos[cur].p, inv.p, orig[cur].p, frc[cur].p, frc_side.p, res.spread, vp, vp && req.lang);
             prof.end(6, stream);
-            if (vp) { step_done = true; ++n_fused_steps; pend_a = nullptr; frc_valid = false; return; }
+            if (vp) { res.step = true; ++n_fused_steps; pend_a = nullptr; frc_valid = false; return res; }
             pend_a = frc_side.p;
             frc_valid = true;
-            return;
+            return res;
         }
-        if (bonded.any()) { prof.begin(5, stream); bonded.launch_forces(stream, G, I, pos[cur].p, inv.p, frc[cur].p, orig[cur].p, n_owned, cap, terms_fused); prof.end(5, stream); }
+        if (bonded.any()) { prof.begin(5, stream); bonded.launch_forces(stream, G, I, pos[cur].p, inv.p, frc[cur].p, orig[cur].p, n_owned, cap, res.terms); prof.end(5, stream); }
         launch_pme_forces();
         frc_valid = true;
+        return res;
     }
     // frc[cur] += the second force array, for consumers other than the second kick
     void fold_side_forces() {
@@ -1637,12 +1658,10 @@ template <class T> class Engine final : public EngineBase {
     // The energy variant of the pair kernel also writes forces: they go to a scratch array (kept by the context: no allocation per
     // call on the logging path), the forces the integrator carries stay where they are.
     DBuf<T4> frc_scratch; DBuf<unsigned long long> nl_counter;
-    T4* frc_override = nullptr;
     void energy_pass() {
         frc_scratch.reserve(cap);
-        frc_override = frc_scratch.p;
-        try { launch_pair_kernel(true); } catch (...) { frc_override = nullptr; throw; }
-        frc_override = nullptr;
+        PassReq req; req.frc = frc_scratch.p;
+        launch_pair_kernel(true, 0, false, req);
     }
     double potential_energy(int64_t step_n) override {
         ensure_built(step_n);
@@ -2051,24 +2070,18 @@ template <class T> class Engine final : public EngineBase {
         const bool solo = hp.n_cm_peers == 0 && hp.n_send_rows == 0;              // no peers: the partials of the launch before are the whole sum
         // … which workgroup 0 of the pair pass in between adds up into ONE partial, as inside mhip_vv_run (ForceArgs::cm_fin_in): the integrator's blocks
         // then do not each re-sum hundreds of partials first
-        cm_fin_solo_src = (solo && halo_cm_in && n_ghost == 0 && pending_cm.n > 1 && pending_cm.n <= 4096) ? (const double*)cm_step.p + (size_t)(cm_half ^ 1) * 4 * 1024 : (const double*)nullptr;
-        cm_fin_solo_done = false;
-        step_forces(step_n);
-        cm_fin_solo_src = nullptr;
+        PassReq req;
+        req.cm_sum_in = (solo && halo_cm_in && n_ghost == 0 && pending_cm.n > 1 && pending_cm.n <= 4096) ? (const double*)cm_step.p + (size_t)(cm_half ^ 1) * 4 * 1024 : (const double*)nullptr;
+        const bool summed = step_forces(step_n, req).cm_summed;
         flush_cm();                                                               // (a removal registered through the stepwise entry points)
-        const double* cm_in = halo_cm_in ? (solo ? (cm_fin_solo_done ? (const double*)cm_fin_buf.p : (const double*)cm_step.p + (size_t)(cm_half ^ 1) * 4 * 1024) : (const double*)cm_all.p) : (const double*)nullptr;
-        const int n_in = solo ? (cm_fin_solo_done ? 1 : pending_cm.n) : 1 + hp.n_cm_peers;
+        const double* cm_in = halo_cm_in ? (solo ? (summed ? (const double*)cm_fin_buf.p : (const double*)cm_step.p + (size_t)(cm_half ^ 1) * 4 * 1024) : (const double*)cm_all.p) : (const double*)nullptr;
+        const int n_in = solo ? (summed ? 1 : pending_cm.n) : 1 + hp.n_cm_peers;
         // (block count: mhip_vv_run's — fewer, longer blocks at these sizes, see there)
         const int nb = (cm && last) ? n_parts : std::min(cdiv(n_owned, 256), solo ? (int)std::max<int64_t>(256, std::min<int64_t>(512, n_owned / 2048)) : 1024);
         double* cm_out = cm ? (last ? cm_parts_dev : cm_step.p + (size_t)(solo ? cm_half : 0) * 4 * 1024) : (double*)nullptr;
         prof.begin(2, stream);
         tr("k_vv_mid");
-        auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, stream, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, T(dt), T(dt) / T(2),
-                               cm_in, n_in, cm_out, (const T4*)pend_a, G, (const T4*)nullptr, (const T4*)nullptr, (float*)nullptr);
-        };
-        if (last) { if (cm) go(k_vv_mid<T, true, true>); else go(k_vv_mid<T, false, true>); }
-        else { if (cm) go(k_vv_mid<T, true, false>); else go(k_vv_mid<T, false, false>); }
+        vv_mid_launch(cm, last, nb, dt, cm_in, n_in, cm_out, false);
         prof.end(2, stream);
         pend_a = nullptr; pending_cm.none();
         if (due && !dual) refresh(step_n);
@@ -2558,13 +2571,22 @@ template <class T> class Engine final : public EngineBase {
     }
     void rebuild_now(int64_t step_n) override { flush_cm(); resolve_track(step_n); lists_after_set_state(); if (stale) rebuild(step_n); else refresh(step_n); }
 
-    // the tail of a step whose force pass integrated (step_done, of vv_loop and langevin_run): the check it measured is issued for trk_at, the Σ m v
+    // the tail of a step whose force pass integrated (res.step, of vv_loop and langevin_run): the check it measured is issued for trk_at, the Σ m v
     // partials it left in cm_blk are pending removal, frc[cur] belongs to the coordinates before the drift
-    void after_fused_step(bool measure, int64_t trk_at, bool cm) {
-        step_done = false;
-        if (measure) issue_track(step_parts, trk_at);
+    void after_fused_step(const PassRes& res, bool measure, int64_t trk_at, bool cm) {
+        if (measure) issue_track(res.parts, trk_at);
         pend_a = nullptr; pending_cm.none(); frc_valid = false;
-        if (cm) { pending_cm.resum(cm_blk.p + (size_t)step_half * 4 * step_parts, step_parts); step_half ^= 1; }
+        if (cm) { pending_cm.resum(cm_blk.p + (size_t)step_half * 4 * res.parts, res.parts); step_half ^= 1; }
+    }
+    // one k_vv_mid launch of nb blocks (last: the closing kick alone); measure: the maxima of the next step's check into trk_part
+    void vv_mid_launch(bool cm, bool last, int nb, double dt, const double* cm_in, int n_in, double* cm_out, bool measure) {
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, stream, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, T(dt), T(dt) / T(2),
+                               cm_in, n_in, cm_out, (const T4*)pend_a, G,
+                               measure ? (const T4*)pos_snap_in.p : (const T4*)nullptr, measure ? (const T4*)pos_snap.p : (const T4*)nullptr, measure ? trk_part.p : (float*)nullptr);
+        };
+        if (last) { if (cm) go(k_vv_mid<T, true, true>); else go(k_vv_mid<T, false, true>); }
+        else { if (cm) go(k_vv_mid<T, true, false>); else go(k_vv_mid<T, false, false>); }
     }
 
     void vv_run(int64_t first_step, int64_t n_steps, double dt, int remove_cm_every) override {
@@ -2574,8 +2596,8 @@ template <class T> class Engine final : public EngineBase {
         InRun guard_in_run(in_run);
         if (first_step == 0 && remove_cm_every != 0) remove_cm();                 // simulators.jl:563
         vv_init(first_step);                                                      // :564-571
-        if (con_on) { con_run_start(); vv_loop_con(first_step, n_steps, dt, remove_cm_every); }
-        else vv_loop(first_step, n_steps, dt, remove_cm_every, nullptr, 0);
+        if (con_on) con_run_start();
+        vv_loop(first_step, n_steps, dt, remove_cm_every, nullptr, 0);
         flush_cm();
         if (con_on) con_read_back();
         MHIP_HIP(hipGetLastError());
@@ -2584,16 +2606,26 @@ template <class T> class Engine final : public EngineBase {
     }
     // the step loop of a single domain: forces of first_step are in place.  cm_parts_last (nullable): where the LAST step leaves its Σ m v partials (n_parts_last
     // blocks) instead of registering their removal with the context — mhip_domain_run on one brick, whose caller sums them over the (one) rank.
+    // With constraints (simulators.jl:589-620) k_con_step takes the integrator's places: the first kick, RATTLE, drift and SHAKE once, then ONE launch between
+    // consecutive force passes (closing kick, RATTLE, Σ m v, next kick, RATTLE, drift, SHAKE, velocity correction, wrap), the closing kick + RATTLE at the end.
+    // No force launch integrates then (they update one atom per lane and cannot see a cluster's partners).
     void vv_loop(int64_t first_step, int64_t n_steps, double dt, int remove_cm_every, double* cm_parts_last, int n_parts_last) {
         const int every = rebuild_every();
         // fused stepping: first kick + drift once, then ONE integrator launch between consecutive force passes (k_vv_mid), the
-        // plain second kick at the end.  A thermostat needs v_n between the kicks: the two-launch form then.
+        // plain second kick at the end.  A thermostat needs v_n between the kicks: the two-launch form then (never with constraints: set_andersen refuses them).
         const bool fused = !(andersen_prob > 0);
         InRun guard_fused(in_vv_fused); in_vv_fused = fused;
         const bool pre = dual;                                                    // without the dual list: the reference's order
         const int64_t last = first_step + n_steps;
         int half = 0;
-        if (fused && n_steps > 0) vv_stage1(dt);
+        if (fused && n_steps > 0) {
+            if (con_on) {
+                prof.begin(2, stream);
+                con_launch(0, con_blocks(), dt, nullptr, false, nullptr);
+                prof.end(2, stream);
+                pending_cm.none(); frc_valid = false;
+            } else vv_stage1(dt);
+        }
         for (int64_t step = first_step + 1; step <= last; ++step) {
             if (!fused) vv_stage1(dt);                                            // :594-609
             // find_neighbors at step % n_steps == 0 (:645, neighbors.jl:396) builds the list from the coordinates of THIS step; it is
@@ -2610,14 +2642,14 @@ template <class T> class Engine final : public EngineBase {
             }
             // the validity check of step + 1 is measured where its coordinates are made: by this step's integrator launch — or by the pair pass itself when it integrates
             const bool measure = step != last && async_ok() && !trk_issued && check_due(step + 1, every);
-            step_req.on = step != last && !bonded.any() && !pme.on(); step_req.cm = cm;      // (one kernel either way: its stage time is its own, so the stage timers leave it fused)
-            step_req.gcv = step != last && bonded.any() && pme.on() && (pre || !check_due(step, every));      // (a re-sort behind the pass would want the total force array)
-            step_req.measure = measure; step_req.dt = dt;
-            step_done = false;
-            step_forces(step);
-            step_req.on = step_req.gcv = false;
-            if (step_done) {      // the pair pass integrated on the way (k_forces STEP): no integrator launch for this step
-                after_fused_step(measure, step + 1, cm);
+            const bool integrate = step != last && !con_on;
+            PassReq req;
+            req.step = integrate && !bonded.any() && !pme.on(); req.cm = cm;      // (one kernel either way: its stage time is its own, so the stage timers leave it fused)
+            req.gcv = integrate && bonded.any() && pme.on() && (pre || !check_due(step, every));      // (a re-sort behind the pass would want the total force array)
+            req.measure = measure; req.dt = dt;
+            const PassRes res = step_forces(step, req);
+            if (res.step) {      // the pair pass integrated on the way (k_forces STEP): no integrator launch for this step
+                after_fused_step(res, measure, step + 1, cm);
                 continue;
             }
             if (!pre && check_due(step, every)) { fold_side_forces(); refresh(step); }   // the sort permutes vel / frc with the atoms; Σ m v does not care
@@ -2625,20 +2657,14 @@ template <class T> class Engine final : public EngineBase {
             // re-read 32 MB from L2 per launch — more than the 21 MB of atoms of the 256k-atom fluid (13.0 → 10.0 µs with 256 blocks;
             // 1M atoms: 21.2 → 20.2 µs with 512, 21.8 with 256)
             const bool parts_out = step == last && cm && cm_parts_last != nullptr;
-            const int nb = parts_out ? n_parts_last : std::min(cdiv(n_owned, 256), (int)std::max<int64_t>(256, std::min<int64_t>(512, n_owned / 2048)));
-            const double* cm_in = pending_cm.parts_arg();
+            const int nb = con_on ? con_blocks() : parts_out ? n_parts_last : std::min(cdiv(n_owned, 256), (int)std::max<int64_t>(256, std::min<int64_t>(512, n_owned / 2048)));
             double* cm_out = cm ? (parts_out ? cm_parts_last : cm_step.p + (size_t)half * 4 * 1024) : (double*)nullptr;
             prof.begin(2, stream);
             // the speeds for a check that the next step's force pass will measure (see resolve_track); evaluated behind the pass: a prune inside it makes the lists checkable again
             const bool measure_mid = step != last && async_ok() && !trk_issued && check_due(step + 1, every);
-            if (measure_mid) { trk_part.reserve(3 * (size_t)std::max(n_blocks, 1024)); trk_out.reserve(4); }
-            auto go = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, stream, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, T(dt), T(dt) / T(2),
-                                   cm_in, pending_cm.n, cm_out, (const T4*)pend_a, G,
-                                   measure_mid ? (const T4*)pos_snap_in.p : (const T4*)nullptr, measure_mid ? (const T4*)pos_snap.p : (const T4*)nullptr, measure_mid ? trk_part.p : (float*)nullptr);
-            };
-            if (step == last) { if (cm) go(k_vv_mid<T, true, true>); else go(k_vv_mid<T, false, true>); }
-            else { if (cm) go(k_vv_mid<T, true, false>); else go(k_vv_mid<T, false, false>); }
+            if (measure_mid) trk_reserve(n_blocks);
+            if (con_on) con_launch(step == last ? 2 : 1, nb, dt, cm_out, measure_mid, nullptr);
+            else vv_mid_launch(cm, step == last, nb, dt, pending_cm.parts_arg(), pending_cm.n, cm_out, measure_mid);
             prof.end(2, stream);
             if (measure_mid) issue_track(nb, step + 1);   // the check of step + 1, read by resolve_track at step + 2
             if (step == last) frc_run_total = pend_a == nullptr && n_ghost == 0;   // (side arrays are added by the kick, not folded)
@@ -2698,42 +2724,6 @@ template <class T> class Engine final : public EngineBase {
         launch_con_step<T>(stream, nb, mode, C, A, G);
         MHIP_HIP(hipGetLastError());
     }
-    // vv_loop with constraints (simulators.jl:589-620): the first kick, RATTLE, drift and SHAKE once, then ONE k_con_step between consecutive
-    // force passes (closing kick, RATTLE, Σ m v, next kick, RATTLE, drift, SHAKE, velocity correction, wrap), the closing kick + RATTLE at the
-    // end.  No force launch integrates (they update one atom per lane and cannot see a cluster's partners).
-    void vv_loop_con(int64_t first_step, int64_t n_steps, double dt, int remove_cm_every) {
-        const int every = rebuild_every();
-        InRun guard_fused(in_vv_fused); in_vv_fused = true;      // (the list checks measured by k_con_step; Σ m v partials summed down by the pair pass)
-        const bool pre = dual;
-        const int64_t last = first_step + n_steps;
-        const int nb = con_blocks();
-        int half = 0;
-        if (n_steps > 0) {
-            prof.begin(2, stream);
-            con_launch(0, nb, dt, nullptr, false, nullptr);
-            prof.end(2, stream);
-            pending_cm.none(); frc_valid = false;
-        }
-        for (int64_t step = first_step + 1; step <= last; ++step) {
-            if (trk_issued && step > trk_step) resolve_track(step);
-            if (pre && check_due(step, every)) refresh(step);
-            const bool cm = remove_cm_every != 0 && step % remove_cm_every == 0;
-            step_forces(step);
-            if (!pre && check_due(step, every)) { fold_side_forces(); refresh(step); }
-            const bool measure_mid = step != last && async_ok() && !trk_issued && check_due(step + 1, every);
-            if (measure_mid) { trk_part.reserve(3 * (size_t)std::max(n_blocks, 1024)); trk_out.reserve(4); }
-            double* cm_out = cm ? cm_step.p + (size_t)half * 4 * 1024 : (double*)nullptr;
-            prof.begin(2, stream);
-            con_launch(step == last ? 2 : 1, nb, dt, cm_out, measure_mid, nullptr);
-            prof.end(2, stream);
-            if (measure_mid) issue_track(nb, step + 1);
-            if (step == last) frc_run_total = pend_a == nullptr;
-            pend_a = nullptr; pending_cm.none();
-            if (cm) { pending_cm.resum(cm_out, nb); half ^= 1; }
-            if (step != last) frc_valid = false;
-        }
-    }
-
     // ---- stochastic dynamics (kernels in stochastic.hip) ------------------------------------------------------
     StochP<T> stoch_params(double kT, uint64_t key, uint64_t ctr1) const {
         StochP<T> P{};
@@ -2795,12 +2785,11 @@ template <class T> class Engine final : public EngineBase {
             // a small system's step (bonded terms + PME): its last force launch — interpolation + bonded sums — runs the update as well (step_fused.h, k_gather_collect_vv<…, LANG>),
             // every step of the run: a Langevin step is complete in itself, there is no closing half kick to keep a launch for
             const bool measure = in_lang_async && async_ok() && !trk_issued && check_due(step, every);      // the check refresh(step) below would make with a drained stream
-            step_req.gcv = bonded.any() && pme.on() && !con_on; step_req.on = !bonded.any() && !pme.on() && !con_on; step_req.lang = &P; step_req.cm = cm; step_req.measure = measure; step_req.dt = dt;      // (on: the packed fp32 one-type pass runs the update in its epilogue, k_forces<…, STEP, ·, LANG>)
-            step_done = false;
-            step_forces(step);                                                    // :1173
-            step_req.gcv = step_req.on = false; step_req.lang = nullptr; step_req.measure = false;
-            if (step_done) {
-                after_fused_step(measure, step, cm);
+            PassReq req;
+            req.gcv = bonded.any() && pme.on() && !con_on; req.step = !bonded.any() && !pme.on() && !con_on; req.lang = &P; req.cm = cm; req.measure = measure; req.dt = dt;      // (step: the packed fp32 one-type pass runs the update in its epilogue, k_forces<…, STEP, ·, LANG>)
+            const PassRes res = step_forces(step, req);                          // :1173
+            if (res.step) {
+                after_fused_step(res, measure, step, cm);
                 apply_coupling(step);
                 if (check_due(step, every)) refresh(step);
                 continue;
@@ -2808,7 +2797,7 @@ template <class T> class Engine final : public EngineBase {
             prof.begin(2, stream);
             double* cm_out = cm ? cm_step.p + (size_t)half * 4 * 1024 : (double*)nullptr;   // the other half may still be read by this launch
             if (con_on) {      // kick, RATTLE, half drift, O-step, half drift, SHAKE per cluster (simulators.jl:1176-1201)
-                if (measure) { trk_part.reserve(3 * (size_t)std::max(n_blocks, 1024)); trk_out.reserve(4); }
+                if (measure) trk_reserve(n_blocks);
                 con_launch(3, nb, dt, cm_out, measure, &P);
                 if (measure) issue_track(nb, step);
             } else
