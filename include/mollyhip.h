@@ -316,6 +316,31 @@ int32_t mhip_set_constraints(mhip_ctx* ctx, int64_t n_dist, const int32_t* i, co
  * in the last run; the count of cluster-solves that stopped at max_iters since set; spare */
 int32_t mhip_constraint_info(mhip_ctx* ctx, int64_t* out8);
 
+/* ---- virtual sites (src/virtual.jl) ------------------------------------------------------------------------------------------------ */
+/* n sites; type 1/2/3/4 = OneParticleSite / TwoParticleAverageSite / ThreeParticleAverageSite / OutOfPlaneSite (virtual.jl:10-22);
+ * 0-based caller indices (a2, a3 = -1 where unused); w6 = per site (weight_1, weight_2, weight_3, weight_12, weight_13,
+ * weight_cross [1/nm]); host arrays.  n = 0 removes the sites: the context then steps as one that never had any.
+ * Validation as setup_virtual_sites (virtual.jl:120-180): MHIP_ERR_INVALID for a type outside 1..4, an index out of range, an atom defined as a
+ * site twice, a parent that is itself a site, a site that is in a constraint (either call order with mhip_set_constraints), weights of a type 2 / 3
+ * site that do not sum to 1 (isapprox).  MHIP_ERR_UNSUPPORTED with ghosts or a domain plan, a TriclinicBoundary or the Andersen coupling; the split
+ * step and the halo paths refuse a context with sites.  mhip_vv_run and mhip_langevin_run then serve every site inside the work item that owns all
+ * of its parents (a constraint cluster, a free atom, or 2..4 free atoms joined for the purpose): its force joins the parents' before every kick, its
+ * position follows them after every drift, its velocity is left alone.  They refuse (when the run starts) a site with a non-zero mass
+ * (MHIP_ERR_INVALID) and a site no single item can host (MHIP_ERR_UNSUPPORTED: parents in two constraint clusters, or a union of free parents above
+ * four atoms).  mhip_forces, mhip_specific_forces, mhip_general_forces, the energies and the virials do not change: they return per-atom forces with
+ * the sites' own rows in them, as the reference's loops do before distribute_forces!; mhip_remove_cm and mhip_andersen leave a site's velocity alone,
+ * mhip_random_velocities sets it to zero (spatial.jl:807-831, 910, 926; kernels.jl:696, 712). */
+int32_t mhip_set_virtual_sites(mhip_ctx* ctx, int64_t n, const int32_t* type, const int32_t* site, const int32_t* a1,
+                               const int32_t* a2, const int32_t* a3, const double* w6);
+/* place_virtual_sites! (virtual.jl:187-224) on the context's coordinates */
+int32_t mhip_place_virtual_sites(mhip_ctx* ctx);
+/* distribute_forces! (virtual.jl:226-294) in place on the CALLER's packed xyz array (caller order, the context's precision): every site's row is
+ * added to its parents' rows and zeroed.  Linear in f, so a caller may distribute the parts or their sum.  An OutOfPlaneSite reads the context's
+ * current coordinates. */
+int32_t mhip_distribute_forces(mhip_ctx* ctx, void* f_xyz, int32_t mem_kind);
+/* out[8]: sites of type 1..4; hosted sites; work items that host one; unconstrained groups formed; spare */
+int32_t mhip_virtual_site_info(mhip_ctx* ctx, int64_t* out8);
+
 /* ---- neighbour list export (bit-exact check) ------------------------------------------------ */
 /* Half list, each unordered pair once with i < j (0-based), special flag as neighbors.jl:411.
  * Pair SET equals the reference's for the same-precision arithmetic; order is unspecified.

@@ -81,6 +81,21 @@ function push_constraints!(c::HipContext, sys::System{3, <:ROCArray, T}) where T
                    c.ptr, length(di), di, dj, dd, length(ai), ai, aj, ak, d3, Float64(ustrip(sr.dist_tolerance)), Float64(ustrip(sr.vel_tolerance)), Int32(sr.max_iters)))
 end
 
+# Virtual sites (src/virtual.jl) from sys.virtual_sites into the engine: inside mhip_vv_run / mhip_langevin_run every site is served by the work item that owns
+# its parents (force gathered before the kick, position written behind the wrap); the engine validates the set as setup_virtual_sites does and refuses, when
+# a run starts, what it cannot host.  The one-shot overrides need nothing: Molly's own forces! calls distribute_forces! behind them.
+function push_virtual_sites!(c::HipContext, sys::System{3, <:ROCArray, T}) where T
+    vs = Array(sys.virtual_sites)
+    isempty(vs) && return
+    i32(f) = Int32[f(v) for v in vs]
+    w6 = Float64[]
+    for v in vs
+        append!(w6, (Float64(v.weight_1), Float64(v.weight_2), Float64(v.weight_3), Float64(v.weight_12), Float64(v.weight_13), Float64(ustrip(v.weight_cross))))
+    end
+    check(c, ccall((:mhip_set_virtual_sites, libmollyhip), Int32, (Ptr{Cvoid}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+                   c.ptr, length(vs), i32(v -> v.type), i32(v -> v.atom_ind - 1), i32(v -> v.atom_1 - 1), i32(v -> v.atom_2 - 1), i32(v -> v.atom_3 - 1), w6))
+end
+
 # The reference reads sys.atoms, sys.boundary, sys.pairwise_inters and the neighbour finder's exception caches at EVERY call (ext/MollyCUDAExt.jl:845-873); the
 # engine keeps them in its context, so every look-up checks that what it keeps is still what the System holds: a replaced boundary goes through mhip_set_box, a
 # replaced atoms array through mhip_set_atoms, new exception pairs through mhip_set_exceptions, a replaced interaction tuple makes a new context.
@@ -114,6 +129,7 @@ function context!(sys::System{3, <:ROCArray, T}, inters::Tuple=sys.pairwise_inte
             check(c, ccall((:mhip_set_triclinic, libmollyhip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int32), c.ptr, bv, approx ? 1 : 0))
         end
         no_list || push_constraints!(c, sys)
+        no_list || push_virtual_sites!(c, sys)
         lock(CONTEXTS_LOCK) do
             table[sys] = c
         end
@@ -175,9 +191,8 @@ function engine_energy!(pe_vec_nounits, sys::System{3, <:ROCArray, T}, c::HipCon
 end
 
 # ≙ ext/MollyCUDAExt.jl:2373 (generic spatial.jl:920): v .-= Σ m v / Σ m in place on sys.velocities.  Virtual sites (the
-# `has_vs` branch of ext:2442-2449) are outside the engine's scope: such systems keep the generic method.
+# `has_vs` branch of ext:2442-2449) keep their velocity: the engine skips the atoms push_virtual_sites! named.
 function remove_CM_motion!(sys::System{3, <:ROCArray, T}) where T
-    isempty(sys.virtual_sites) || return invoke(remove_CM_motion!, Tuple{System}, sys)
     c = context!(sys)
     check(c, ccall((:mhip_set_state, libmollyhip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32), c.ptr, devptr(sys.coords), devptr(sys.velocities), 1))
     check(c, ccall((:mhip_remove_cm, libmollyhip), Int32, (Ptr{Cvoid},), c.ptr))

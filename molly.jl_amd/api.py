@@ -326,6 +326,49 @@ class SHAKE_RATTLE:
         return len(self.dist_constraints) + 3 * len(self.angle_constraints)     # n_dof_lost (constraints.jl:358-372)
 
 
+class VirtualSite:
+    """VirtualSite (virtual.jl:10-22) with 0-based atom numbers (−1: unused): type 1/2/3/4 = OneParticleSite / TwoParticleAverageSite /
+    ThreeParticleAverageSite / OutOfPlaneSite; weights that do not apply are zero; weight_cross in 1/nm."""
+    __slots__ = ("type", "atom_ind", "atom_1", "atom_2", "atom_3", "weight_1", "weight_2", "weight_3", "weight_12", "weight_13", "weight_cross")
+
+    def __init__(self, type, atom_ind, atom_1, atom_2=-1, atom_3=-1, weight_1=0.0, weight_2=0.0, weight_3=0.0, weight_12=0.0, weight_13=0.0, weight_cross=0.0):
+        self.type, self.atom_ind, self.atom_1, self.atom_2, self.atom_3 = int(type), int(atom_ind), int(atom_1), int(atom_2), int(atom_3)
+        self.weight_1, self.weight_2, self.weight_3 = float(weight_1), float(weight_2), float(weight_3)
+        self.weight_12, self.weight_13, self.weight_cross = float(weight_12), float(weight_13), float(weight_cross)
+
+    @property
+    def weights(self):
+        return (self.weight_1, self.weight_2, self.weight_3, self.weight_12, self.weight_13, self.weight_cross)
+
+
+def _isapprox_one(x):
+    return abs(x - 1.0) <= math.sqrt(np.finfo(np.float64).eps) * max(abs(x), 1.0)      # isapprox(x, 1), default rtol
+
+
+def OneParticleSite(atom_ind, atom_1):
+    """r = r₁ (virtual.jl:38-55)"""
+    return VirtualSite(1, atom_ind, atom_1)
+
+
+def TwoParticleAverageSite(atom_ind, atom_1, atom_2, weight_1, weight_2):
+    """r = w₁ r₁ + w₂ r₂ with w₁ + w₂ = 1 (virtual.jl:57-76)"""
+    if not _isapprox_one(weight_1 + weight_2):
+        raise ValueError(f"weight_1 + weight_2 must equal 1 for a TwoParticleAverageSite, found {weight_1 + weight_2}")
+    return VirtualSite(2, atom_ind, atom_1, atom_2, weight_1=weight_1, weight_2=weight_2)
+
+
+def ThreeParticleAverageSite(atom_ind, atom_1, atom_2, atom_3, weight_1, weight_2, weight_3):
+    """r = w₁ r₁ + w₂ r₂ + w₃ r₃ with w₁ + w₂ + w₃ = 1 (virtual.jl:78-98)"""
+    if not _isapprox_one(weight_1 + weight_2 + weight_3):
+        raise ValueError(f"weight_1 + weight_2 + weight_3 must equal 1 for a ThreeParticleAverageSite, found {weight_1 + weight_2 + weight_3}")
+    return VirtualSite(3, atom_ind, atom_1, atom_2, atom_3, weight_1=weight_1, weight_2=weight_2, weight_3=weight_3)
+
+
+def OutOfPlaneSite(atom_ind, atom_1, atom_2, atom_3, weight_12, weight_13, weight_cross):
+    """r = r₁ + w₁₂ r₁₂ + w₁₃ r₁₃ + w_cross (r₁₂ × r₁₃) (virtual.jl:100-118); not compatible with the virial"""
+    return VirtualSite(4, atom_ind, atom_1, atom_2, atom_3, weight_12=weight_12, weight_13=weight_13, weight_cross=weight_cross)
+
+
 def _rng(rng):
     return rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
 
@@ -341,7 +384,7 @@ class System:
 
     def __init__(self, atoms=None, coords=None, boundary=None, velocities=None, pairwise_inters=(),
                  specific_inter_lists=(), neighbor_finder=None, dtype=np.float32, device_id=0,
-                 charge=None, sigma=None, eps=None, mass=None, general_inters=(), lam=None, constraints=()):
+                 charge=None, sigma=None, eps=None, mass=None, general_inters=(), lam=None, constraints=(), virtual_sites=()):
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
             raise ValueError("dtype must be float32 or float64")
@@ -377,6 +420,27 @@ class System:
                 raise MollyHipError(-6, f"constraint algorithm {type(c).__name__} is outside the hot-path scope")
         if len(self.constraints) > 1:
             raise MollyHipError(-6, "one SHAKE_RATTLE per System")
+        self.virtual_sites = tuple(virtual_sites)
+        self.virtual_site_flags = np.zeros(n, bool)       # setup_virtual_sites (virtual.jl:120-180); the engine repeats these checks and adds its own
+        for vi, vs in enumerate(self.virtual_sites):
+            if not isinstance(vs, VirtualSite) or vs.type not in (1, 2, 3, 4):
+                raise ValueError(f"unrecognised virtual site {vi}: type should be 1/2/3/4")
+            if not 0 <= vs.atom_ind < n:
+                raise ValueError(f"virtual site {vi} defines atom number {vs.atom_ind} but there are only {n} atoms present")
+            if self.virtual_site_flags[vs.atom_ind]:
+                raise ValueError(f"virtual site {vi} defines atom number {vs.atom_ind} but a previous virtual site already defined this atom")
+            self.virtual_site_flags[vs.atom_ind] = True
+        for vi, vs in enumerate(self.virtual_sites):
+            for a in (vs.atom_1, vs.atom_2, vs.atom_3)[:(1, 2, 3, 3)[vs.type - 1]]:
+                if not 0 <= a < n:
+                    raise ValueError(f"virtual site {vi} has a parent atom out of range")
+                if self.virtual_site_flags[a]:
+                    raise ValueError(f"virtual site {vi} is defined in terms of an atom that is itself a virtual site")
+        for sr in self.constraints:
+            for c in list(sr.dist_constraints) + list(sr.angle_constraints):
+                for a in (c.i, c.j) + ((c.k,) if hasattr(c, "k") else ()):
+                    if 0 <= a < n and self.virtual_site_flags[a]:
+                        raise ValueError(f"atom {a} is a virtual site but is also in a constraint")
         self.total_mass = float(self.masses.sum(dtype=np.float64))
         self._pushed_atoms = False
 
@@ -525,9 +589,26 @@ class System:
             self._check(L.mhip_set_constraints(self._ctx, len(ci), *map(self._ptr, (ci, cj, cd)), len(ai), *map(self._ptr, (ai, aj, ak, d3)),
                                                sr.dist_tolerance, sr.vel_tolerance, sr.max_iters))
 
+        if self.virtual_sites:
+            vs = self.virtual_sites
+            cols = [i32([getattr(v, k) for v in vs]) for k in ("type", "atom_ind", "atom_1", "atom_2", "atom_3")]
+            w6 = np.ascontiguousarray([v.weights for v in vs], dtype=np.float64).reshape(-1)
+            self._check(L.mhip_set_virtual_sites(self._ctx, len(vs), *map(self._ptr, cols), self._ptr(w6)))
+
     @property
     def n_constraints(self):
         return sum(c.n_constraints for c in self.constraints)
+
+    def virtual_site_info(self):
+        """mhip_virtual_site_info: sites of each type, sites hosted by a work item of the step loops, items that host one, unconstrained groups formed"""
+        out = (C.c_int64 * 8)()
+        self._check(_lib.lib().mhip_virtual_site_info(self.engine(), C.byref(out)))
+        keys = ("one_particle", "two_particle", "three_particle", "out_of_plane", "n_hosted", "n_host_items", "n_groups")
+        return dict(zip(keys, list(out)[:7]))
+
+    def _refuse_sites(self, what):
+        if self.virtual_sites:
+            raise MollyHipError(-6, f"{what} of a System with virtual sites is not supported")
 
     def constraint_info(self):
         """mhip_constraint_info: clusters of 2 / 3 / 4 atoms, angle clusters, constraints, the most SHAKE iterations of the last run,
@@ -580,13 +661,26 @@ def forces(sys, step_n=0, pairwise=True, specific=True, general=True):
         sys._check(L.mhip_specific_forces(sys._ctx, 1, sys._ptr(out), _lib.MEM_HOST))
     if general and sys.general_inters:
         sys._check(L.mhip_general_forces(sys._ctx, 1, sys._ptr(out), _lib.MEM_HOST))
+    if sys.virtual_sites:                                         # distribute_forces! on the total (force.jl:796)
+        sys._check(L.mhip_distribute_forces(sys._ctx, sys._ptr(out), _lib.MEM_HOST))
     return out
+
+
+def place_virtual_sites(sys):
+    """place_virtual_sites!(sys) (virtual.jl:187-224): the sites' coordinates from their parents', on the device"""
+    if sys.virtual_sites:
+        sys.push_state(velocities=True)
+        sys._check(_lib.lib().mhip_place_virtual_sites(sys._ctx))
+        sys.pull_state()
+    return sys
 
 
 def virial(sys, step_n=0, pairwise=True, specific=True, general=True):
     """virial(sys): 3×3 tensor Σ r ⊗ f of the pairwise (over the neighbour pairs, force.jl:848-852), specific (force.jl:991-1060) and
     general (PME reciprocal space, ewald.jl:701-723, 925-927) interactions (energy.jl:116-131)."""
     sys._refuse_constrained("virial")
+    if any(vs.type == 4 for vs in sys.virtual_sites):
+        raise MollyHipError(-6, "OutOfPlaneSite is not currently compatible with virial calculation (virtual.jl:112)")
     L = _lib.lib()
     sys.push_state(velocities=False)
     v = np.zeros(9, np.float64)
@@ -645,8 +739,8 @@ def kinetic_energy(sys):
 
 
 def temperature(sys):
-    """T = 2 KE / (df k), df = 3N − 3 − n_constraints for a fully periodic box (energy.jl:158-175, constraints.jl:358-380)."""
-    return 2 * kinetic_energy(sys) / ((3 * len(sys) - 3 - sys.n_constraints) * BOLTZMANN)
+    """T = 2 KE / (df k), df = 3(N − n_sites) − 3 − n_constraints for a fully periodic box (energy.jl:158-175, constraints.jl:358-380, types.jl:957-959)."""
+    return 2 * kinetic_energy(sys) / ((3 * (len(sys) - len(sys.virtual_sites)) - 3 - sys.n_constraints) * BOLTZMANN)
 
 
 def total_energy(sys):
@@ -729,6 +823,7 @@ def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
     reference it supplies the Philox key / counter words and the barostat's uniform numbers."""
     if isinstance(sim, SteepestDescentMinimizer):
         sys._refuse_constrained("minimization")
+        sys._refuse_sites("minimization")
         if init_step < 0:
             raise ValueError("init_step must be non-negative")
         return _minimize(sys, sim, init_step)
@@ -749,6 +844,9 @@ def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
         raise ValueError("init_step must be non-negative")
     if barostat is not None:
         sys._refuse_constrained("MonteCarloBarostat coupling")
+        sys._refuse_sites("MonteCarloBarostat coupling")
+    if thermostat is not None and sys.virtual_sites:
+        raise MollyHipError(-6, "AndersenThermostat coupling of a System with virtual sites is not supported")
     if thermostat is not None and sys.constraints:
         raise MollyHipError(-6, "AndersenThermostat coupling of a constrained System is not supported")
     L = _lib.lib()
@@ -835,6 +933,7 @@ def scale_coords(sys, scale_matrix, scale_velocities=False):
     """scale_coords!(sys, μ; ignore_molecules=true) (spatial.jl:1184-1210, the branch of systems without a topology — every atom a molecule): box B′ = μ B,
     r′ = μ r in the system's number type, optionally v′ = μ⁻¹ v.  The rigid-molecule branch (:1211-1290) is host code on molecule lists and stays outside the
     engine; what the engine must do is follow the boundary (mhip_set_box)."""
+    sys._refuse_sites("scale_coords")
     mu = np.asarray(scale_matrix, dtype=sys.dtype).reshape(3, 3)
     diagonal = not np.any(mu != np.diag(np.diag(mu)))
     b = sys.boundary
@@ -918,6 +1017,7 @@ def _apply_mc_barostat(sys, barostat, step_n, rng, energy=None):
     """apply_coupling!(sys, buffers, ::MonteCarloBarostat, sim, neighbors, step_n; rng) (coupling.jl:861-884).  `energy`: the potential-energy function (tests
     put the oracle's here to replay the same random numbers on the CPU)."""
     sys._refuse_constrained("MonteCarloBarostat coupling")
+    sys._refuse_sites("MonteCarloBarostat coupling")
     if step_n % barostat.n_steps != 0:
         return False
     energy = energy or (lambda s: potential_energy(s, step_n))

@@ -8,6 +8,9 @@
 // the wrap.  Atoms outside every cluster are one-atom work items of the same grid.  The items are laid out by kind, each kind
 // padded to a whole wave, so a wave never diverges on kind.  Atoms are addressed through inv[] (caller index → slot), so the
 // engine's re-sorts need no remapping.
+//
+// The same lanes serve virtual sites (virtual_sites.h): a site whose parents are all atoms of one item is HOSTED by it — its force joins the
+// parents' before the kick, its position is written behind the wrap.  Parents that are free atoms are joined into unconstrained groups for that.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -15,10 +18,13 @@
 
 #include "common.h"
 #include "stochastic.h"
+#include "virtual_sites.h"
 
 namespace mhip {
 
-enum { CK_2 = 0, CK_3, CK_4, CK_ANGLE, CK_FREE, CK_N };   // work-item kinds, in layout order
+// work-item kinds, in layout order.  CK_G2..4: unconstrained groups — 2..4 free atoms joined into one item only because virtual sites hang off them
+// (kicks, drift and wrap per atom, no solve); they exist only while sites are set
+enum { CK_2 = 0, CK_3, CK_4, CK_ANGLE, CK_FREE, CK_G2, CK_G3, CK_G4, CK_N };
 // one wave per workgroup: a lane's cluster solve is long and serial, so the 6mrr's ≈ 5 600 items are spread over ≈ 90 CUs instead of 22
 constexpr int CON_BLOCK = 64;
 
@@ -28,14 +34,22 @@ constexpr int CON_BLOCK = 64;
 struct ClusterSet {
     std::vector<int32_t> atoms;
     std::vector<double> d;
-    int32_t end[CK_N] = {0, 0, 0, 0, 0};   // end of each kind's (padded) item range
+    int32_t end[CK_N] = {};                // end of each kind's (padded) item range
     int64_t n_kind[4] = {0, 0, 0, 0};      // clusters of 2 / 3 / 4 atoms, angle clusters
     int64_t n_constraints = 0;             // degrees of freedom removed
+    // hosted virtual sites (virtual_sites.h): a site whose parents are all atoms of ONE item is served by that item's lane.  Side table:
+    // item t hosts the vs_item[2t + 1] sites from number vs_item[2t] on; site s is vs_rec[4s ..] = (type, caller index of the site atom,
+    // local parent numbers l1 | l2 << 8 | l3 << 16, ·) with weights vs_w[6s ..].  A site atom is never an item of its own.
+    std::vector<int32_t> vs_item, vs_rec;
+    std::vector<double> vs_w;
+    int64_t n_hosted = 0, n_host_items = 0, n_groups = 0;
+    int64_t first_unhosted = -1;           // the first site no single item can host (parents in two clusters, or a union of free parents above four atoms)
+    int32_t n_items() const { return end[CK_N - 1]; }
 };
 // throws ApiError{MHIP_ERR_INVALID} on what SHAKE_RATTLE cannot take: an atom in two clusters, more than three constraints on one
-// centre, a chain, a ring, a linear angle, an index out of range, a non-positive length
+// centre, a chain, a ring, a linear angle, an index out of range, a non-positive length, a virtual site in a constraint (virtual.jl:174-178)
 ClusterSet build_clusters(int64_t n_atoms, int64_t n_dist, const int32_t* i, const int32_t* j, const double* dist,
-                          int64_t n_angle, const int32_t* ai, const int32_t* aj, const int32_t* ak, const double* d3);
+                          int64_t n_angle, const int32_t* ai, const int32_t* aj, const int32_t* ak, const double* d3, const SiteSet* vs = nullptr);
 
 template <class T> struct ConP {
     const int32_t* atoms; const double* d; const int32_t* inv;
@@ -43,6 +57,7 @@ template <class T> struct ConP {
     double tol;                    // SHAKE: | |r| − d | <= tol for every constraint of the cluster
     int32_t max_iters;
     unsigned long long* stat;      // [0] += cluster-solves that stopped at max_iters, [1] = max(iterations any cluster took)
+    const int32_t* vs_item; const int32_t* vs_rec; const double* vs_w;      // hosted virtual sites (null: none)
 };
 
 // what one launch reads and writes besides the clusters

@@ -11,7 +11,7 @@ namespace mhip {
 
 // ---- host: clusters (constraints.jl:251-344) ---------------------------------------------------------------------------------------
 ClusterSet build_clusters(int64_t n_atoms, int64_t n_dist, const int32_t* ci, const int32_t* cj, const double* dist,
-                          int64_t n_angle, const int32_t* ai, const int32_t* aj, const int32_t* ak, const double* d3) {
+                          int64_t n_angle, const int32_t* ai, const int32_t* aj, const int32_t* ak, const double* d3, const SiteSet* vs) {
     auto bad = [](const std::string& m) { return ApiError{MHIP_ERR_INVALID, "constraints: " + m}; };
     if (n_dist < 0 || n_angle < 0) throw bad("negative count");
     if (n_dist > 0 && (!ci || !cj || !dist)) throw bad("null distance-constraint array");
@@ -84,21 +84,114 @@ ClusterSet build_clusters(int64_t n_atoms, int64_t n_dist, const int32_t* ci, co
         Cl cl{}; cl.kind = CK_ANGLE; cl.a[0] = a[0]; cl.a[1] = a[1]; cl.a[2] = a[2]; cl.a[3] = -1; cl.d[0] = d[0]; cl.d[1] = d[1]; cl.d[2] = d[2];
         cls[CK_ANGLE].push_back(cl);
     }
-    // layout: kind by kind, each padded to a whole wave, then the free atoms
-    auto pad = [&]() { while (cs.atoms.size() % (4 * WAVE)) { cs.atoms.push_back(-1); cs.d.push_back(0); } };
+    // virtual sites: which item owns all the parents of each (constraints.h)
+    const bool sites = vs && vs->n > 0;
+    struct Host { int32_t type, site, l[3]; const double* w; };
+    std::vector<std::vector<Host>> hosts[CK_N];
+    for (int k = 0; k < 4; ++k) hosts[k].resize(cls[k].size());
+    std::vector<int32_t> group((size_t)(sites ? n_atoms : 0));      // union of the free parents
+    std::vector<std::vector<int32_t>> members;                       // … and the atoms of each union, ascending
+    std::vector<int32_t> group_no((size_t)(sites ? n_atoms : 0), -1);
+    if (sites) {
+        for (int64_t a = 0; a < n_atoms; ++a)
+            if (vs->flag[a] && owner[a] != -1) throw bad("atom " + std::to_string(a) + " is a virtual site but is also in a constraint");
+        std::vector<int32_t> it_kind((size_t)n_atoms, -1), it_idx((size_t)n_atoms, -1), it_loc((size_t)n_atoms, -1);
+        for (int k = 0; k < 4; ++k)
+            for (size_t q = 0; q < cls[k].size(); ++q)
+                for (int m = 0; m < 4; ++m)
+                    if (cls[k][q].a[m] >= 0) { it_kind[cls[k][q].a[m]] = k; it_idx[cls[k][q].a[m]] = (int32_t)q; it_loc[cls[k][q].a[m]] = m; }
+        std::iota(group.begin(), group.end(), 0);
+        auto gfind = [&](int32_t a) { while (group[a] != a) { group[a] = group[group[a]]; a = group[a]; } return a; };
+        auto unhosted = [&](int64_t s) { if (cs.first_unhosted < 0 || s < cs.first_unhosted) cs.first_unhosted = s; };
+        std::vector<int8_t> where((size_t)vs->n, 0);                 // 1: a cluster hosts it, 2: its parents are free, 0: nobody can
+        for (int64_t s = 0; s < vs->n; ++s) {
+            const int32_t par[3] = {vs->a1[s], vs->a2[s], vs->a3[s]};
+            int n_in = 0, n_free = 0, np = 0; bool same = true;
+            for (int32_t x : par) {
+                if (x < 0) continue;
+                ++np;
+                if (it_kind[x] >= 0) { ++n_in; same = same && it_kind[x] == it_kind[par[0]] && it_idx[x] == it_idx[par[0]]; } else ++n_free;
+            }
+            if (n_in == np && same) {
+                Host h{vs->type[s], vs->site[s], {0, 0, 0}, vs->w.data() + 6 * s};
+                for (int m = 0; m < 3; ++m) h.l[m] = par[m] >= 0 ? it_loc[par[m]] : 0;
+                hosts[it_kind[par[0]]][it_idx[par[0]]].push_back(h);
+                where[s] = 1;
+            } else if (n_free == np) {
+                for (int m = 1; m < 3; ++m) if (par[m] >= 0) group[gfind(par[m])] = gfind(par[0]);
+                where[s] = 2;
+            } else unhosted(s);
+        }
+        for (int64_t s = 0; s < vs->n; ++s) {
+            if (where[s] != 2) continue;
+            for (int32_t x : {vs->a1[s], vs->a2[s], vs->a3[s]})
+                if (x >= 0 && group_no[gfind(x)] < 0) { group_no[gfind(x)] = (int32_t)members.size(); members.emplace_back(); }
+        }
+        for (int64_t a = 0; a < n_atoms; ++a) {                      // ascending: the local numbers follow the caller's order
+            if (owner[a] != -1 || vs->flag[a]) continue;
+            const int32_t g = group_no[gfind((int32_t)a)];
+            if (g >= 0) { members[g].push_back((int32_t)a); group_no[a] = g; }
+        }
+        for (int k = CK_FREE; k < CK_N; ++k) hosts[k].resize(members.size());      // (indexed by union number; a union lands in one kind)
+        for (int64_t s = 0; s < vs->n; ++s) {
+            if (where[s] != 2) continue;
+            const int32_t par[3] = {vs->a1[s], vs->a2[s], vs->a3[s]};
+            const auto& mem = members[group_no[par[0]]];
+            if (mem.size() > 4) { unhosted(s); continue; }
+            Host h{vs->type[s], vs->site[s], {0, 0, 0}, vs->w.data() + 6 * s};
+            for (int m = 0; m < 3; ++m) h.l[m] = par[m] >= 0 ? (int32_t)(std::find(mem.begin(), mem.end(), par[m]) - mem.begin()) : 0;
+            hosts[mem.size() == 1 ? CK_FREE : CK_G2 + (int)mem.size() - 2][group_no[par[0]]].push_back(h);
+        }
+    }
+    // layout: kind by kind, each padded to a whole wave, then the free atoms (then, with sites, the unconstrained groups)
+    auto item = [&](const int32_t* a, const double* d, const std::vector<Host>* hs) {
+        for (int m = 0; m < 4; ++m) { cs.atoms.push_back(a[m]); cs.d.push_back(m < 3 ? d[m] : 0.0); }
+        if (!sites) return;
+        cs.vs_item.push_back((int32_t)(cs.vs_rec.size() / 4)); cs.vs_item.push_back(hs ? (int32_t)hs->size() : 0);
+        if (!hs || hs->empty()) return;
+        ++cs.n_host_items; cs.n_hosted += (int64_t)hs->size();
+        for (const Host& h : *hs) {
+            cs.vs_rec.push_back(h.type); cs.vs_rec.push_back(h.site); cs.vs_rec.push_back(h.l[0] | (h.l[1] << 8) | (h.l[2] << 16)); cs.vs_rec.push_back(0);
+            cs.vs_w.insert(cs.vs_w.end(), h.w, h.w + 6);
+        }
+    };
+    const int32_t none4[4] = {-1, -1, -1, -1}; const double zero3[3] = {0, 0, 0};
+    auto pad = [&]() { while (cs.atoms.size() % (4 * WAVE)) item(none4, zero3, nullptr); };
     for (int k = 0; k < 4; ++k) {
-        for (const Cl& cl : cls[k]) {
-            for (int m = 0; m < 4; ++m) cs.atoms.push_back(cl.a[m]);
-            for (int m = 0; m < 3; ++m) cs.d.push_back(k == CK_2 && m > 0 ? 0.0 : (k == CK_3 && m > 1 ? 0.0 : cl.d[m]));
-            cs.d.push_back(0);
+        for (size_t q = 0; q < cls[k].size(); ++q) {
+            const Cl& cl = cls[k][q];
+            const double d[3] = {cl.d[0], k == CK_2 ? 0.0 : cl.d[1], (k == CK_2 || k == CK_3) ? 0.0 : cl.d[2]};
+            item(cl.a, d, sites ? &hosts[k][q] : nullptr);
         }
         pad();
         cs.end[k] = (int32_t)(cs.atoms.size() / 4);
         cs.n_kind[k] = (int64_t)cls[k].size();
     }
-    for (int64_t a = 0; a < n_atoms; ++a)
-        if (owner[a] == -1) { cs.atoms.push_back((int32_t)a); cs.atoms.push_back(-1); cs.atoms.push_back(-1); cs.atoms.push_back(-1); for (int m = 0; m < 4; ++m) cs.d.push_back(0); }
+    for (int64_t a = 0; a < n_atoms; ++a) {
+        if (owner[a] != -1 || (sites && vs->flag[a])) continue;      // (a site atom is nobody's work item: nothing integrates it)
+        const int32_t g = sites ? group_no[a] : -1;
+        if (g >= 0 && members[g].size() >= 2 && members[g].size() <= 4) continue;
+        const int32_t one[4] = {(int32_t)a, -1, -1, -1};
+        item(one, zero3, g >= 0 && members[g].size() == 1 ? &hosts[CK_FREE][g] : nullptr);
+    }
     cs.end[CK_FREE] = (int32_t)(cs.atoms.size() / 4);
+    for (int k = CK_G2; k < CK_N; ++k) {
+        const size_t na = (size_t)(k - CK_G2 + 2);
+        bool any = false;
+        for (size_t g = 0; g < members.size(); ++g) {
+            if (members[g].size() != na) continue;
+            if (!any) {                                              // the free atoms, or the groups before, end on a whole wave
+                const int32_t was = cs.end[k - 1];
+                pad(); any = true;
+                for (int j = k - 1; j >= CK_FREE && cs.end[j] == was; --j) cs.end[j] = (int32_t)(cs.atoms.size() / 4);
+            }
+            int32_t a4[4] = {-1, -1, -1, -1};
+            for (size_t m = 0; m < na; ++m) a4[m] = members[g][m];
+            item(a4, zero3, &hosts[k][g]);
+            ++cs.n_groups;
+        }
+        cs.end[k] = (int32_t)(cs.atoms.size() / 4);
+    }
     cs.n_constraints = n_dist + 3 * n_angle;
     return cs;
 }
@@ -112,6 +205,9 @@ template <> struct Shape<CK_3> { static constexpr int NA = 3, NC = 2; };
 template <> struct Shape<CK_4> { static constexpr int NA = 4, NC = 3; };
 template <> struct Shape<CK_ANGLE> { static constexpr int NA = 3, NC = 3; };
 template <> struct Shape<CK_FREE> { static constexpr int NA = 1, NC = 0; };
+template <> struct Shape<CK_G2> { static constexpr int NA = 2, NC = 0; };
+template <> struct Shape<CK_G3> { static constexpr int NA = 3, NC = 0; };
+template <> struct Shape<CK_G4> { static constexpr int NA = 4, NC = 0; };
 // constraint c joins local atoms ca → cb (r = x_cb − x_ca): the centre to its c-th partner, or the triangle (0,1), (1,2), (0,2)
 template <int K> __device__ constexpr int ca(int c) { return K == CK_ANGLE ? (c == 1 ? 1 : 0) : 0; }
 template <int K> __device__ constexpr int cb(int c) { return K == CK_ANGLE ? (c == 0 ? 1 : 2) : c + 1; }
@@ -236,6 +332,71 @@ template <class T, int K> __device__ inline int shake(const typename Vec<T>::T4*
     return done ? it : -it;
 }
 
+// ---- hosted virtual sites (virtual_sites.h): the sites whose parents are all atoms of this item ------------------------------------------
+// the position of the item's atom with local number l.  Selected with bit masks: written as a chain of conditional copies the compiler turns the choice
+// back into an indexed load, and p[] — with it the whole item — moves from registers to scratch memory.
+__device__ inline float mask_if(float v, bool c) { return __uint_as_float(__float_as_uint(v) & (c ? 0xffffffffu : 0u)); }
+__device__ inline double mask_if(double v, bool c) { return __longlong_as_double(__double_as_longlong(v) & (c ? -1ll : 0ll)); }
+__device__ inline float bits_or(float a, float b) { return __uint_as_float(__float_as_uint(a) | __float_as_uint(b)); }
+__device__ inline double bits_or(double a, double b) { return __longlong_as_double(__double_as_longlong(a) | __double_as_longlong(b)); }
+template <class T, int NA> __device__ inline typename Vec<T>::T4 pick(const typename Vec<T>::T4* p, int l) {
+    typename Vec<T>::T4 r;
+    r.x = mask_if(p[0].x, l == 0); r.y = mask_if(p[0].y, l == 0); r.z = mask_if(p[0].z, l == 0); r.w = T(0);
+#pragma unroll
+    for (int k = 1; k < NA; ++k) { r.x = bits_or(r.x, mask_if(p[k].x, l == k)); r.y = bits_or(r.y, mask_if(p[k].y, l == k)); r.z = bits_or(r.z, mask_if(p[k].z, l == k)); }
+    return r;
+}
+// distribute_forces! for the item's sites: each site's force (of the positions p the forces were computed at) joins its parents' in f[]
+template <class T, int NA>
+__device__ inline void sites_gather(const ConP<T>& C, const ConStep<T>& A, const GridP<T>& G, int first, int n_vs, const typename Vec<T>::T4* p, typename Vec<T>::T4* f) {
+    using T4 = typename Vec<T>::T4;
+    for (int j = 0; j < n_vs; ++j) {
+        const int32_t* r = C.vs_rec + 4 * (int64_t)(first + j);
+        const int type = r[0], l1 = r[2] & 255, l2 = (r[2] >> 8) & 255, l3 = (r[2] >> 16) & 255;
+        const int32_t ss = C.inv[r[1]];
+        T4 fs = A.frc[ss];
+        if (A.fa) { const T4 ga = A.fa[ss]; fs.x += ga.x; fs.y += ga.y; fs.z += ga.z; }
+        const T fv[3] = {fs.x, fs.y, fs.z};
+        T f1[3], f2[3], f3[3];
+        vs_shares<T>(type, pick<T, NA>(p, l1), pick<T, NA>(p, l2), pick<T, NA>(p, l3), C.vs_w + 6 * (int64_t)(first + j), G, fv, f1, f2, f3);
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            const bool c1 = k == l1, c2 = type >= VS_TWO_AVG && k == l2, c3 = type >= VS_THREE_AVG && k == l3;      // (masked adds: see pick)
+            f[k].x += mask_if(f1[0], c1); f[k].y += mask_if(f1[1], c1); f[k].z += mask_if(f1[2], c1);
+            f[k].x += mask_if(f2[0], c2); f[k].y += mask_if(f2[1], c2); f[k].z += mask_if(f2[2], c2);
+            f[k].x += mask_if(f3[0], c3); f[k].y += mask_if(f3[1], c3); f[k].z += mask_if(f3[2], c3);
+        }
+    }
+}
+// place_virtual_sites! for the item's sites from the wrapped positions p; the sites join the list-validity maxima as the item's atoms do
+// (a site with a weight outside [0, 1] or a cross term can move farther than any parent), their speed taken from the move itself
+template <class T, int NA>
+__device__ inline void sites_place(const ConP<T>& C, const ConStep<T>& A, const GridP<T>& G, int first, int n_vs, const typename Vec<T>::T4* p, T dt, float& da, float& db, float& v2) {
+    for (int j = 0; j < n_vs; ++j) {
+        const int32_t* r = C.vs_rec + 4 * (int64_t)(first + j);
+        const int type = r[0], l1 = r[2] & 255, l2 = (r[2] >> 8) & 255, l3 = (r[2] >> 16) & 255;
+        const int32_t ss = C.inv[r[1]];
+        auto q = A.pos[ss];
+        T x, y, z;
+        vs_position<T>(type, pick<T, NA>(p, l1), pick<T, NA>(p, l2), pick<T, NA>(p, l3), C.vs_w + 6 * (int64_t)(first + j), G, x, y, z);
+        if (A.trk_part) {
+            T ex = x - q.x, ey = y - q.y, ez = z - q.z;
+            disp_image(ex, ey, ez, G);
+            v2 = fmaxf(v2, (float)((ex * ex + ey * ey + ez * ez) / (dt * dt)));
+            auto s = A.snap_a[ss];
+            ex = x - s.x; ey = y - s.y; ez = z - s.z;
+            disp_image(ex, ey, ez, G);
+            da = fmaxf(da, (float)(ex * ex + ey * ey + ez * ez));
+            s = A.snap_b[ss];
+            ex = x - s.x; ey = y - s.y; ez = z - s.z;
+            disp_image(ex, ey, ez, G);
+            db = fmaxf(db, (float)(ex * ex + ey * ey + ez * ez));
+        }
+        q.x = x; q.y = y; q.z = z;
+        A.pos[ss] = q;
+    }
+}
+
 struct Acc { double px = 0, py = 0, pz = 0, m = 0; float da = 0.f, db = 0.f, v2 = 0.f; int max_it = 0; int n_fail = 0; };
 
 // one work item: the arithmetic of k_vv1 / k_vv_mid / k_langevin per atom, with RATTLE after every kick and SHAKE after every drift
@@ -259,6 +420,8 @@ __device__ inline void con_item(const ConP<T>& C, const ConStep<T>& A, const Gri
         }
         im[k] = v[k].w == T(0) ? 0.0 : 1.0 / (double)v[k].w;
     }
+    const int vs_first = C.vs_item ? C.vs_item[2 * t] : 0, n_vs = C.vs_item ? C.vs_item[2 * t + 1] : 0;
+    if (n_vs > 0) sites_gather<T, NA>(C, A, G, vs_first, n_vs, p, f);                                                // force.jl:796, before the first use of f
     T kx[NA], ky[NA], kz[NA];
     if constexpr (MODE == 1 || MODE == 2) {
 #pragma unroll
@@ -313,6 +476,7 @@ __device__ inline void con_item(const ConP<T>& C, const ConStep<T>& A, const Gri
 #pragma unroll
                 for (int k = 0; k < NA; ++k) { acc.px += (double)v[k].x * v[k].w; acc.py += (double)v[k].y * v[k].w; acc.pz += (double)v[k].z * v[k].w; acc.m += v[k].w; }
     }
+    if (n_vs > 0 && (MODE != 2 || sub)) sites_place<T, NA>(C, A, G, vs_first, n_vs, p, MODE == 3 ? A.S.dt : A.dt, acc.da, acc.db, acc.v2);   // :610 / :1187, wherever the parents moved
 #pragma unroll
     for (int k = 0; k < NA; ++k) {
         if (MODE != 2 || sub) A.pos[sl[k]] = p[k];
@@ -339,13 +503,16 @@ __global__ void __launch_bounds__(CON_BLOCK) k_con_step(ConP<T> C, ConStep<T> A,
     else if (A.vcm) { vc[0] = A.vcm[0]; vc[1] = A.vcm[1]; vc[2] = A.vcm[2]; }
     const T sh[3] = {M<T>::mul(vc[0], A.dt), M<T>::mul(vc[1], A.dt), M<T>::mul(vc[2], A.dt)};
     Acc acc;
-    const int64_t n = C.end[CK_FREE], stride = (int64_t)gridDim.x * blockDim.x;      // (a multiple of the wave: a wave stays within one kind)
+    const int64_t n = C.end[CK_N - 1], stride = (int64_t)gridDim.x * blockDim.x;      // (a multiple of the wave: a wave stays within one kind)
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += stride) {
         if (t < C.end[CK_2]) con_item<T, CK_2, MODE>(C, A, G, t, vc, sub, sh, acc);
         else if (t < C.end[CK_3]) con_item<T, CK_3, MODE>(C, A, G, t, vc, sub, sh, acc);
         else if (t < C.end[CK_4]) con_item<T, CK_4, MODE>(C, A, G, t, vc, sub, sh, acc);
         else if (t < C.end[CK_ANGLE]) con_item<T, CK_ANGLE, MODE>(C, A, G, t, vc, sub, sh, acc);
-        else con_item<T, CK_FREE, MODE>(C, A, G, t, vc, sub, sh, acc);
+        else if (t < C.end[CK_FREE]) con_item<T, CK_FREE, MODE>(C, A, G, t, vc, sub, sh, acc);
+        else if (t < C.end[CK_G2]) con_item<T, CK_G2, MODE>(C, A, G, t, vc, sub, sh, acc);
+        else if (t < C.end[CK_G3]) con_item<T, CK_G3, MODE>(C, A, G, t, vc, sub, sh, acc);
+        else con_item<T, CK_G4, MODE>(C, A, G, t, vc, sub, sh, acc);
     }
     // the solver's counters: one vector atomic per wave into device words the host reads with the run's other read-backs
     int mi = acc.max_it;

@@ -16,6 +16,7 @@
 #include "bonded.h"
 #include "stochastic.h"
 #include "constraints.h"
+#include "virtual_sites.h"
 #include "pme.h"
 #include "step_fused.h"
 #include "hilbert.h"
@@ -107,6 +108,11 @@ struct EngineBase {
     virtual void set_constraints(int64_t, const int32_t*, const int32_t*, const double*, int64_t, const int32_t*, const int32_t*, const int32_t*, const double*, double, double, int32_t) = 0;
     virtual void constraint_info(int64_t*) = 0;
     virtual bool constrained() const = 0;
+    virtual void set_virtual_sites(int64_t, const int32_t*, const int32_t*, const int32_t*, const int32_t*, const int32_t*, const double*) = 0;
+    virtual void place_virtual_sites() = 0;
+    virtual void distribute_forces(void*, int) = 0;
+    virtual void virtual_site_info(int64_t*) = 0;
+    virtual bool has_sites() const = 0;
     virtual void domain_export(int64_t*, void*) = 0;
 };
 
@@ -314,7 +320,7 @@ template <class T> class Engine final : public EngineBase {
         if (ev_prune) (void)hipEventDestroy(ev_prune);
         if (h_red) (void)hipHostFree(h_red);
         if (h_con) (void)hipHostFree(h_con);
-        con_atoms.release(); con_d.release(); con_stat.release();
+        con_atoms.release(); con_d.release(); con_stat.release(); vs_item.release(); vs_hrec.release(); vs_hw.release(); vs_rec.release(); vs_w.release(); vs_flag.release();
         if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
 
@@ -553,7 +559,7 @@ template <class T> class Engine final : public EngineBase {
     void flush_cm() {
         if (!pending_cm.mode()) return;
         hipLaunchKernelGGL(k_shift_vel<T>, dim3(std::min(cdiv(n_owned, 256), 1024)), dim3(256), 0, stream, n_owned, vel[cur].p, (const T*)vcm.p,
-                           pending_cm.parts_arg(), pending_cm.n);
+                           pending_cm.parts_arg(), pending_cm.n, vs_on ? (const int32_t*)orig[cur].p : nullptr, (const uint8_t*)vs_flag.p);      // (spatial.jl:926: a site's velocity is left alone)
         pending_cm.none();
     }
 
@@ -1477,6 +1483,7 @@ template <class T> class Engine final : public EngineBase {
         if (no <= 0 || ng < 0 || no + ng > cap) throw ApiError{MHIP_ERR_INVALID, "atom counts exceed the context capacity"};
         if (ng > 0 && tri_mode) throw ApiError{MHIP_ERR_UNSUPPORTED, "TriclinicBoundary is single-domain"};
         if (ng > 0 && con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain"};
+        if (ng > 0 && vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites run on a single domain"};
         n_owned = no; n_ghost = ng; n_tot = no + ng;
         // new local atom set: restart from the identity order
         hipLaunchKernelGGL(k_iota2, dim3(std::min(cdiv(n_tot, 256), 1024)), dim3(256), 0, stream, n_tot, orig[cur].p, inv.p);
@@ -1518,7 +1525,7 @@ template <class T> class Engine final : public EngineBase {
         if (want_eshift() != eshift) stale = true;   // the lists in use are in the other entry format
         pc_valid = false;   // Σq, Σq² of the PME self / net-charge terms are read back only when an energy asks for them
         s3.release(); s4.release(); s5.release();
-        params_set = true; frc_valid = false;
+        params_set = true; frc_valid = false; vs_mass_ok = false;
     }
 
     void set_exceptions(const int32_t* ei, const int32_t* ej, int64_t ne, const int32_t* si, const int32_t* sj, int64_t ns) override {
@@ -1581,7 +1588,7 @@ template <class T> class Engine final : public EngineBase {
             // Whether the lists still cover every cutoff sphere is decided by displacement at the next force call (lists_after_set_state);
             // lists that have no skin to spend are rebuilt at once, as before.
             if (!stale && (dual || lazy_single)) coords_moved = true; else stale = true;
-            frc_valid = false; state_set = true;
+            frc_valid = false; state_set = true; vs_place_due = vs_on;
         }
     }
 
@@ -1726,6 +1733,7 @@ template <class T> class Engine final : public EngineBase {
         for (int d = 0; d < 3; ++d) if (!cfg.periodic[d]) throw ApiError{MHIP_ERR_UNSUPPORTED, "TriclinicBoundary is periodic on all three axes"};
         if (n_ghost > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "TriclinicBoundary: single domain"};
         if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints with a TriclinicBoundary are not supported"};
+        if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites with a TriclinicBoundary are not supported"};
         if (std::fabs(bv9[0] - cfg.box[0]) > 1e-12 * bv9[0] || std::fabs(bv9[4] - cfg.box[1]) > 1e-12 * bv9[4] || std::fabs(bv9[8] - cfg.box[2]) > 1e-12 * bv9[8])
             throw ApiError{MHIP_ERR_INVALID, "the context's box must be (v1.x, v2.y, v3.z) of the triclinic basis"};
         MHIP_HIP(hipStreamSynchronize(stream));
@@ -1884,6 +1892,7 @@ template <class T> class Engine final : public EngineBase {
     }
     void vv_stage1(double dt) override {
         if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no constraints: use mhip_vv_run"};
+        if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no virtual sites: use mhip_vv_run"};
         if (!frc_valid) throw ApiError{MHIP_ERR_STATE, "vv_stage1 needs forces from vv_init / vv_stage2"};
         cur_dt = dt;
         tr("k_vv1");
@@ -1919,6 +1928,7 @@ template <class T> class Engine final : public EngineBase {
     }
     void vv_stage2(int64_t step_n, double dt) override {
         if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no constraints: use mhip_vv_run"};
+        if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no virtual sites: use mhip_vv_run"};
         stage2_cadenced(step_n, dt, false);
         MHIP_HIP(hipGetLastError());
     }
@@ -2050,6 +2060,7 @@ template <class T> class Engine final : public EngineBase {
     // cm_parts_dev as n_parts per-block partials for an all-reduce, nothing is packed) — at the rebuild cadence and at the end of a run
     void halo_mid(int64_t step_n, double dt, int32_t flags, double* cm_parts_dev, int32_t n_parts) override {
         if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain, stepped by mhip_vv_run / mhip_langevin_run"};
+        if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites run on a single domain, stepped by mhip_vv_run / mhip_langevin_run"};
         if (!hp_set) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_plan first"};
         const bool cm = (flags & 1) != 0, last = (flags & 2) != 0;
         if (cm && last && (!cm_parts_dev || n_parts < 1 || n_parts > 1024)) throw ApiError{MHIP_ERR_INVALID, "n_parts must be 1..1024"};
@@ -2252,6 +2263,7 @@ template <class T> class Engine final : public EngineBase {
     // (mhip_remove_cm_parts_dev), as after mhip_vv_halo_mid with the stop flag.  counters[0..2] += checks, prunes arranged, re-plans asked.
     void domain_run(int64_t first_step, int64_t n_steps, double dt, int32_t remove_cm_every, double* cm_parts_dev, int32_t n_parts, int64_t* steps_done, int32_t* reason, int64_t* counters) override {
         if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain, stepped by mhip_vv_run / mhip_langevin_run"};
+        if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites run on a single domain, stepped by mhip_vv_run / mhip_langevin_run"};
         if (!hp_set) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_plan first"};
         const bool solo = hp.n_cm_peers == 0 && hp.n_send_rows == 0;
         if (!solo && !xf.routes) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_routes first"};
@@ -2370,6 +2382,7 @@ template <class T> class Engine final : public EngineBase {
     void set_domain(const mhip_domain_geometry* gm, const int64_t* gids_dev) override {
         if (!gm) { dom.ready = false; return; }
         if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain"};
+        if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites run on a single domain"};
         if (caller_indexed_topology()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the in-engine re-plan moves atoms between ranks and resets the caller order: contexts with bonded terms, exception lists, special pairs or PME keep the host planner"};
         const int gx = gm->grid[0], gy = gm->grid[1], gz = gm->grid[2];
         if (gx < 1 || gy < 1 || gz < 1 || (int64_t)gx * gy * gz > XFER_MAX_RANKS) throw ApiError{MHIP_ERR_INVALID, "domain geometry: 1 .. 64 bricks"};
@@ -2594,15 +2607,16 @@ template <class T> class Engine final : public EngineBase {
         if (n_ghost > 0) throw ApiError{MHIP_ERR_STATE, "vv_run is single-domain; drive ghosted domains with vv_stage1/vv_stage2"};
         cur_dt = dt;
         InRun guard_in_run(in_run);
+        sites_run_start();                                                        // :561-562
         if (first_step == 0 && remove_cm_every != 0) remove_cm();                 // simulators.jl:563
         vv_init(first_step);                                                      // :564-571
-        if (con_on) con_run_start();
+        if (items_on()) con_run_start();
         vv_loop(first_step, n_steps, dt, remove_cm_every, nullptr, 0);
         flush_cm();
-        if (con_on) con_read_back();
+        if (items_on()) con_read_back();
         MHIP_HIP(hipGetLastError());
         MHIP_HIP(hipStreamSynchronize(stream));
-        if (con_on) con_after_run();
+        if (items_on()) con_after_run();
     }
     // the step loop of a single domain: forces of first_step are in place.  cm_parts_last (nullable): where the LAST step leaves its Σ m v partials (n_parts_last
     // blocks) instead of registering their removal with the context — mhip_domain_run on one brick, whose caller sums them over the (one) rank.
@@ -2619,7 +2633,7 @@ template <class T> class Engine final : public EngineBase {
         const int64_t last = first_step + n_steps;
         int half = 0;
         if (fused && n_steps > 0) {
-            if (con_on) {
+            if (items_on()) {
                 prof.begin(2, stream);
                 con_launch(0, con_blocks(), dt, nullptr, false, nullptr);
                 prof.end(2, stream);
@@ -2642,7 +2656,7 @@ template <class T> class Engine final : public EngineBase {
             }
             // the validity check of step + 1 is measured where its coordinates are made: by this step's integrator launch — or by the pair pass itself when it integrates
             const bool measure = step != last && async_ok() && !trk_issued && check_due(step + 1, every);
-            const bool integrate = step != last && !con_on;
+            const bool integrate = step != last && !items_on();
             PassReq req;
             req.step = integrate && !bonded.any() && !pme.on(); req.cm = cm;      // (one kernel either way: its stage time is its own, so the stage timers leave it fused)
             req.gcv = integrate && bonded.any() && pme.on() && (pre || !check_due(step, every));      // (a re-sort behind the pass would want the total force array)
@@ -2657,13 +2671,13 @@ template <class T> class Engine final : public EngineBase {
             // re-read 32 MB from L2 per launch — more than the 21 MB of atoms of the 256k-atom fluid (13.0 → 10.0 µs with 256 blocks;
             // 1M atoms: 21.2 → 20.2 µs with 512, 21.8 with 256)
             const bool parts_out = step == last && cm && cm_parts_last != nullptr;
-            const int nb = con_on ? con_blocks() : parts_out ? n_parts_last : std::min(cdiv(n_owned, 256), (int)std::max<int64_t>(256, std::min<int64_t>(512, n_owned / 2048)));
+            const int nb = items_on() ? con_blocks() : parts_out ? n_parts_last : std::min(cdiv(n_owned, 256), (int)std::max<int64_t>(256, std::min<int64_t>(512, n_owned / 2048)));
             double* cm_out = cm ? (parts_out ? cm_parts_last : cm_step.p + (size_t)half * 4 * 1024) : (double*)nullptr;
             prof.begin(2, stream);
             // the speeds for a check that the next step's force pass will measure (see resolve_track); evaluated behind the pass: a prune inside it makes the lists checkable again
             const bool measure_mid = step != last && async_ok() && !trk_issued && check_due(step + 1, every);
             if (measure_mid) trk_reserve(n_blocks);
-            if (con_on) con_launch(step == last ? 2 : 1, nb, dt, cm_out, measure_mid, nullptr);
+            if (items_on()) con_launch(step == last ? 2 : 1, nb, dt, cm_out, measure_mid, nullptr);
             else vv_mid_launch(cm, step == last, nb, dt, pending_cm.parts_arg(), pending_cm.n, cm_out, measure_mid);
             prof.end(2, stream);
             if (measure_mid) issue_track(nb, step + 1);   // the check of step + 1, read by resolve_track at step + 2
@@ -2682,29 +2696,130 @@ template <class T> class Engine final : public EngineBase {
     void set_constraints(int64_t n_dist, const int32_t* ci, const int32_t* cj, const double* dist, int64_t n_angle, const int32_t* ai, const int32_t* aj,
                          const int32_t* ak, const double* d3, double dist_tol, double vel_tol, int32_t max_iters) override {
         if (n_dist == 0 && n_angle == 0) {      // removal: the context steps as one that never had constraints
-            con_on = false; con = ClusterSet{}; con_atoms.release(); con_d.release(); con_stat.release(); con_last_max = con_fails = 0;
+            con_on = false; con_in = ConIn{}; con_last_max = con_fails = 0;
+            build_items(con_in, sites);
             return;
         }
         if (n_ghost > 0 || dom.ready || xf.world > 1) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain"};
         if (tri_mode) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints with a TriclinicBoundary are not supported"};
         if (andersen_prob > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen thermostat with constraints is not supported (a re-drawn velocity breaks RATTLE)"};
         if (!(dist_tol > 0) || !(vel_tol > 0) || max_iters < 1) throw ApiError{MHIP_ERR_INVALID, "constraints: tolerances must be positive and max_iters at least 1"};
-        ClusterSet cs = build_clusters(cfg.n_atoms, n_dist, ci, cj, dist, n_angle, ai, aj, ak, d3);
+        if (n_dist < 0 || n_angle < 0 || (n_dist > 0 && (!ci || !cj || !dist)) || (n_angle > 0 && (!ai || !aj || !ak || !d3))) throw ApiError{MHIP_ERR_INVALID, "constraints: negative count or null array"};
+        ConIn in;
+        in.ci.assign(ci, ci + n_dist); in.cj.assign(cj, cj + n_dist); in.dist.assign(dist, dist + n_dist);
+        in.ai.assign(ai, ai + n_angle); in.aj.assign(aj, aj + n_angle); in.ak.assign(ak, ak + n_angle); in.d3.assign(d3, d3 + 3 * n_angle);
+        build_items(in, sites);                 // (throws before anything is replaced)
+        con_in = std::move(in); con_tol = dist_tol; con_iters = max_iters; con_on = true; con_last_max = con_fails = 0;
+    }
+    // the work items of k_con_step from the constraints AND the virtual sites as they now stand (either may be empty); uploads them
+    struct ConIn { std::vector<int32_t> ci, cj, ai, aj, ak; std::vector<double> dist, d3; };
+    ConIn con_in;
+    void build_items(const ConIn& in, const SiteSet& vs) {
+        if (in.ci.empty() && in.ai.empty() && vs.n == 0) {
+            con = ClusterSet{}; con_atoms.release(); con_d.release(); con_stat.release(); vs_item.release(); vs_hrec.release(); vs_hw.release();
+            return;
+        }
+        ClusterSet cs = build_clusters(cfg.n_atoms, (int64_t)in.ci.size(), in.ci.data(), in.cj.data(), in.dist.data(), (int64_t)in.ai.size(), in.ai.data(), in.aj.data(), in.ak.data(), in.d3.data(), &vs);
         MHIP_HIP(hipStreamSynchronize(stream));
         con_atoms.reserve(cs.atoms.size()); con_d.reserve(cs.d.size()); con_stat.reserve(2);
         MHIP_HIP(hipMemcpy(con_atoms.p, cs.atoms.data(), cs.atoms.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         MHIP_HIP(hipMemcpy(con_d.p, cs.d.data(), cs.d.size() * sizeof(double), hipMemcpyHostToDevice));
         MHIP_HIP(hipMemset(con_stat.p, 0, 2 * sizeof(unsigned long long)));
+        if (vs.n > 0) {
+            vs_item.reserve(cs.vs_item.size()); vs_hrec.reserve(cs.vs_rec.size()); vs_hw.reserve(cs.vs_w.size());
+            MHIP_HIP(hipMemcpy(vs_item.p, cs.vs_item.data(), cs.vs_item.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            if (!cs.vs_rec.empty()) MHIP_HIP(hipMemcpy(vs_hrec.p, cs.vs_rec.data(), cs.vs_rec.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            if (!cs.vs_w.empty()) MHIP_HIP(hipMemcpy(vs_hw.p, cs.vs_w.data(), cs.vs_w.size() * sizeof(double), hipMemcpyHostToDevice));
+        } else { vs_item.release(); vs_hrec.release(); vs_hw.release(); }
         if (!h_con) MHIP_HIP(hipHostMalloc((void**)&h_con, 2 * sizeof(unsigned long long)));
         h_con[0] = h_con[1] = 0;
-        con = std::move(cs); con_tol = dist_tol; con_iters = max_iters; con_on = true; con_last_max = con_fails = 0;
+        con = std::move(cs);
+    }
+    bool items_on() const { return con_on || vs_on; }
+
+    // ---- virtual sites (virtual_sites.h): the one-shot entry points; inside the step loops the sites are hosted by the items above -----------
+    SiteSet sites; bool vs_on = false, vs_place_due = false, vs_mass_ok = false;
+    DBuf<int32_t> vs_item, vs_hrec, vs_rec; DBuf<double> vs_hw, vs_w; DBuf<uint8_t> vs_flag;
+    bool has_sites() const override { return vs_on; }
+    void set_virtual_sites(int64_t n, const int32_t* type, const int32_t* site, const int32_t* a1, const int32_t* a2, const int32_t* a3, const double* w6) override {
+        if (n == 0) {      // removal: the context steps as one that never had sites
+            vs_on = false; vs_place_due = false; sites = SiteSet{}; vs_rec.release(); vs_w.release(); vs_flag.release();
+            build_items(con_in, sites);
+            return;
+        }
+        if (n_ghost > 0 || dom.ready || xf.world > 1) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites run on a single domain"};
+        if (tri_mode) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites with a TriclinicBoundary are not supported"};
+        if (andersen_prob > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen thermostat with virtual sites is not supported"};
+        SiteSet vs = build_sites(cfg.n_atoms, n, type, site, a1, a2, a3, w6);
+        build_items(con_in, vs);                // (a site in a constraint: MHIP_ERR_INVALID here, as in mhip_set_constraints when that comes second)
+        std::vector<int32_t> rec(8 * (size_t)n, 0);
+        for (int64_t k = 0; k < n; ++k) { int32_t* r = rec.data() + 8 * k; r[0] = vs.type[k]; r[1] = vs.site[k]; r[2] = vs.a1[k]; r[3] = vs.a2[k]; r[4] = vs.a3[k]; }
+        vs_rec.reserve(rec.size()); vs_w.reserve(vs.w.size()); vs_flag.reserve(vs.flag.size());
+        MHIP_HIP(hipMemcpy(vs_rec.p, rec.data(), rec.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        MHIP_HIP(hipMemcpy(vs_w.p, vs.w.data(), vs.w.size() * sizeof(double), hipMemcpyHostToDevice));
+        MHIP_HIP(hipMemcpy(vs_flag.p, vs.flag.data(), vs.flag.size(), hipMemcpyHostToDevice));
+        sites = std::move(vs); vs_on = true; vs_place_due = state_set; vs_mass_ok = false; frc_run_total = false;
+    }
+    VsP<T> vs_params() const { VsP<T> V{}; V.n = sites.n; V.rec = vs_rec.p; V.w = vs_w.p; V.inv = inv.p; return V; }
+    // place_virtual_sites! on the coordinates the context holds.  To the lists and the forces this is a set_state of the sites' rows: the same protocol
+    // (a site that already sat where its parents put it changes nothing, so a run continued in chunks finds its forces and lists as it left them)
+    void place_virtual_sites() override {
+        if (!state_set) throw ApiError{MHIP_ERR_STATE, "set_state must be called before place_virtual_sites"};
+        vs_place_due = false;
+        if (!vs_on) return;
+        state_changed.reserve(2);
+        if (!state_pending) { MHIP_HIP(hipMemsetAsync(state_changed.p, 0, 2 * sizeof(int32_t), stream)); frc_before_set_state = frc_valid; }
+        state_pending = true;
+        tr("k_vs_place");
+        launch_vs_place<T>(stream, vs_params(), pos[cur].p, G, state_changed.p);
+        MHIP_HIP(hipGetLastError());
+        if (!stale && (dual || lazy_single)) coords_moved = true; else stale = true;
+        frc_valid = false;
+    }
+    // distribute_forces! in place on the caller's packed xyz array (caller order); r12, r13 of an OutOfPlaneSite from the context's coordinates
+    void distribute_forces(void* f_xyz, int mem_kind) override {
+        if (!vs_on) return;
+        if (!state_set && sites.n_type[3] > 0) throw ApiError{MHIP_ERR_STATE, "set_state must be called before distribute_forces (OutOfPlaneSite)"};
+        T* d = (T*)f_xyz;
+        const size_t count = 3 * (size_t)cfg.n_atoms;
+        if (mem_kind == MHIP_MEM_HOST) { stage_a.reserve(count); d = stage_a.p; MHIP_HIP(hipMemcpyAsync(d, f_xyz, count * sizeof(T), hipMemcpyHostToDevice, stream)); }
+        tr("k_vs_spread");
+        launch_vs_spread<T>(stream, vs_params(), (const T4*)pos[cur].p, d, G);
+        MHIP_HIP(hipGetLastError());
+        if (mem_kind == MHIP_MEM_HOST) { MHIP_HIP(hipMemcpyAsync(f_xyz, d, count * sizeof(T), hipMemcpyDeviceToHost, stream)); MHIP_HIP(hipStreamSynchronize(stream)); }
+    }
+    // sites of type 1..4, hosted sites, work items that host one, unconstrained groups formed, spare
+    void virtual_site_info(int64_t* out8) override {
+        for (int k = 0; k < 4; ++k) out8[k] = sites.n_type[k];
+        out8[4] = vs_on ? con.n_hosted : 0; out8[5] = vs_on ? con.n_host_items : 0; out8[6] = vs_on ? con.n_groups : 0; out8[7] = 0;
+    }
+    // the start of a run with sites: what the hosted step relies on is checked here (not in the setters, which then need no call order), and the sites are
+    // placed if coordinates came in since they last were (simulators.jl:561-562, 1113-1114)
+    void sites_run_start() {
+        if (!vs_on) return;
+        if (!state_set || !params_set) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before a run"};
+        if (andersen_prob > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen thermostat with virtual sites is not supported"};
+        if (con.first_unhosted >= 0)
+            throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual site " + std::to_string(con.first_unhosted) + " (atom " + std::to_string(sites.site[con.first_unhosted]) +
+                           ") cannot be hosted by one work item: its parents lie in two constraint clusters, or in a union of free parents above four atoms"};
+        if (!vs_mass_ok) {      // once per set of masses
+            std::vector<T4> hv((size_t)n_owned); std::vector<int32_t> hi((size_t)cfg.n_atoms);
+            MHIP_HIP(hipStreamSynchronize(stream));
+            MHIP_HIP(hipMemcpy(hv.data(), vel[cur].p, hv.size() * sizeof(T4), hipMemcpyDeviceToHost));
+            MHIP_HIP(hipMemcpy(hi.data(), inv.p, hi.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            for (int64_t k = 0; k < sites.n; ++k)
+                if (hv[hi[sites.site[k]]].w != T(0))
+                    throw ApiError{MHIP_ERR_INVALID, "virtual site " + std::to_string(k) + " (atom " + std::to_string(sites.site[k]) + ") has a non-zero mass: the step loops need massless sites"};
+            vs_mass_ok = true;
+        }
+        if (vs_place_due) place_virtual_sites();
     }
     // clusters of 2 / 3 / 4 atoms, angle clusters, constraints, the most SHAKE iterations of the last run, solves stopped at max_iters since set, spare
     void constraint_info(int64_t* out8) override {
         out8[0] = con.n_kind[0]; out8[1] = con.n_kind[1]; out8[2] = con.n_kind[2]; out8[3] = con.n_kind[3];
         out8[4] = con_on ? con.n_constraints : 0; out8[5] = con_last_max; out8[6] = con_fails; out8[7] = 0;
     }
-    int con_blocks() const { return std::max(1, std::min(cdiv(con.end[CK_FREE], CON_BLOCK), 1024)); }      // (<= 1024: the Σ m v partials fit a half of cm_step)
+    int con_blocks() const { return std::max(1, std::min(cdiv(con.n_items(), CON_BLOCK), 1024)); }      // (<= 1024: the Σ m v partials fit a half of cm_step)
     void con_run_start() { MHIP_HIP(hipMemsetAsync(con_stat.p + 1, 0, sizeof(unsigned long long), stream)); }
     // the solver's counters travel with the run's closing synchronisation: no read-back inside the step loop
     void con_read_back() { MHIP_HIP(hipMemcpyAsync(h_con, con_stat.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream)); }
@@ -2714,6 +2829,7 @@ template <class T> class Engine final : public EngineBase {
         ConP<T> C{};
         C.atoms = con_atoms.p; C.d = con_d.p; C.inv = inv.p; for (int k = 0; k < CK_N; ++k) C.end[k] = con.end[k];
         C.tol = con_tol; C.max_iters = con_iters; C.stat = con_stat.p;
+        if (vs_on) { C.vs_item = vs_item.p; C.vs_rec = vs_hrec.p; C.vs_w = vs_hw.p; }
         ConStep<T> A{};
         A.pos = pos[cur].p; A.vel = vel[cur].p; A.frc = frc[cur].p; A.fa = pend_a;
         A.vcm = pending_cm.vcm_arg(vcm.p); A.cm_in = pending_cm.parts_arg(); A.n_cm_in = pending_cm.n; A.cm_out = cm_out;
@@ -2739,7 +2855,7 @@ template <class T> class Engine final : public EngineBase {
         StochP<T> P = stoch_params(kT, key, ctr1);
         const double pc = std::min(std::max(prob, 0.0), std::nextafter(1.0, 0.0));          // clamp(…, 0, prevfloat(1.0))
         P.prob_u64 = (uint64_t)std::nearbyint(std::ldexp(pc, 64));                            // round(UInt64, prob·2⁶⁴) ≤ 2⁶⁴ − 2¹¹
-        launch_redraw<T>(stream, mode, n_owned, vel[cur].p, orig[cur].p, P, pending_cm.vcm_arg(vcm.p), pending_cm.parts_arg(), pending_cm.n);
+        launch_redraw<T>(stream, mode, n_owned, vel[cur].p, orig[cur].p, P, pending_cm.vcm_arg(vcm.p), pending_cm.parts_arg(), pending_cm.n, vs_on ? (const uint8_t*)vs_flag.p : nullptr);
         pending_cm.none();
         MHIP_HIP(hipGetLastError());
     }
@@ -2748,6 +2864,7 @@ template <class T> class Engine final : public EngineBase {
     double andersen_kT = 0, andersen_prob = 0; uint64_t andersen_seed = 0;
     void set_andersen(double kT, double prob, uint64_t seed) override {
         if (prob > 0 && con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen thermostat with constraints is not supported (a re-drawn velocity breaks RATTLE)"};
+        if (prob > 0 && vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen thermostat with virtual sites is not supported"};
         andersen_kT = kT; andersen_prob = prob; andersen_seed = seed;
     }
     void apply_coupling(int64_t step) {
@@ -2766,15 +2883,17 @@ template <class T> class Engine final : public EngineBase {
         const int every = rebuild_every();
         cur_dt = dt;
         InRun guard_in_run(in_run);
-        InRun guard_lang(in_lang_fused); in_lang_fused = bonded.any() && pme.on() && fuse_gcv_env && !con_on;     // (constraints: k_con_step updates whole clusters, no force launch integrates)
-        InRun guard_lang_async(in_lang_async); in_lang_async = (in_lang_fused || con_on || (!bonded.any() && !pme.on() && fuse_step_env)) && !(andersen_prob > 0);
+        sites_run_start();                                                        // :1113-1114
+        const bool items = items_on();                                            // constraints or hosted sites: both stepped by k_con_step
+        InRun guard_lang(in_lang_fused); in_lang_fused = bonded.any() && pme.on() && fuse_gcv_env && !items;     // (constraints: k_con_step updates whole clusters, no force launch integrates)
+        InRun guard_lang_async(in_lang_async); in_lang_async = (in_lang_fused || items || (!bonded.any() && !pme.on() && fuse_step_env)) && !(andersen_prob > 0);
         if (first_step == 0 && remove_cm_every != 0) remove_cm();                 // :1115
         start_lists(first_step);                                                  // :1116
         const double vs = std::exp(-dt * friction);                               // :1091-1092
         StochP<T> P = stoch_params(kT, key, ctr1_0);
         P.dt = T(dt); P.dt_half = T(dt) / T(2); P.vel_scale = T(vs); P.noise_kt = std::sqrt(1.0 - vs * vs) * std::sqrt(kT);
-        const int nb = con_on ? con_blocks() : std::min(cdiv(n_owned, 256), 1024);
-        if (con_on) con_run_start();
+        const int nb = items ? con_blocks() : std::min(cdiv(n_owned, 256), 1024);
+        if (items) con_run_start();
         int half = 0;
         for (int64_t step = first_step + 1; step <= first_step + n_steps; ++step) {
             // a check measured by the update launch of step s (the coordinates x_s it made) is read at the top of step s + 2, behind a whole step of queued work — the
@@ -2786,7 +2905,7 @@ template <class T> class Engine final : public EngineBase {
             // every step of the run: a Langevin step is complete in itself, there is no closing half kick to keep a launch for
             const bool measure = in_lang_async && async_ok() && !trk_issued && check_due(step, every);      // the check refresh(step) below would make with a drained stream
             PassReq req;
-            req.gcv = bonded.any() && pme.on() && !con_on; req.step = !bonded.any() && !pme.on() && !con_on; req.lang = &P; req.cm = cm; req.measure = measure; req.dt = dt;      // (step: the packed fp32 one-type pass runs the update in its epilogue, k_forces<…, STEP, ·, LANG>)
+            req.gcv = bonded.any() && pme.on() && !items; req.step = !bonded.any() && !pme.on() && !items; req.lang = &P; req.cm = cm; req.measure = measure; req.dt = dt;      // (step: the packed fp32 one-type pass runs the update in its epilogue, k_forces<…, STEP, ·, LANG>)
             const PassRes res = step_forces(step, req);                          // :1173
             if (res.step) {
                 after_fused_step(res, measure, step, cm);
@@ -2796,7 +2915,7 @@ template <class T> class Engine final : public EngineBase {
             }
             prof.begin(2, stream);
             double* cm_out = cm ? cm_step.p + (size_t)half * 4 * 1024 : (double*)nullptr;   // the other half may still be read by this launch
-            if (con_on) {      // kick, RATTLE, half drift, O-step, half drift, SHAKE per cluster (simulators.jl:1176-1201)
+            if (items) {      // kick, RATTLE, half drift, O-step, half drift, SHAKE per cluster (simulators.jl:1176-1201)
                 if (measure) trk_reserve(n_blocks);
                 con_launch(3, nb, dt, cm_out, measure, &P);
                 if (measure) issue_track(nb, step);
@@ -2811,10 +2930,10 @@ template <class T> class Engine final : public EngineBase {
             if (check_due(step, every)) refresh(step);                            // :1211 — the next force pass prunes the fresh outer list
         }
         flush_cm();
-        if (con_on) con_read_back();
+        if (items) con_read_back();
         MHIP_HIP(hipGetLastError());
         MHIP_HIP(hipStreamSynchronize(stream));
-        if (con_on) con_after_run();
+        if (items) con_after_run();
     }
 
     int64_t export_neighbors(int32_t* oi, int32_t* oj, uint8_t* osp, int64_t capacity) override { return export_list(oi, oj, osp, capacity, true); }
@@ -3005,6 +3124,7 @@ int32_t mhip_vv_init(mhip_ctx* ctx, int64_t first) {
     NEED_CTX();
     return guard(ctx, [&] {
         if (ctx->e->constrained()) throw mhip::ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no constraints: use mhip_vv_run"};
+        if (ctx->e->has_sites()) throw mhip::ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no virtual sites: use mhip_vv_run"};
         ctx->e->vv_init(first);
     });
 }
@@ -3099,6 +3219,12 @@ int32_t mhip_set_constraints(mhip_ctx* ctx, int64_t n_dist, const int32_t* i, co
     NEED_CTX(); return guard(ctx, [&] { ctx->e->set_constraints(n_dist, i, j, dist, n_angle, ai, aj, ak, d3, dist_tol, vel_tol, max_iters); });
 }
 int32_t mhip_constraint_info(mhip_ctx* ctx, int64_t* out8) { NEED_CTX(); return guard(ctx, [&] { if (!out8) throw mhip::ApiError{MHIP_ERR_INVALID, "null output"}; ctx->e->constraint_info(out8); }); }
+int32_t mhip_set_virtual_sites(mhip_ctx* ctx, int64_t n, const int32_t* type, const int32_t* site, const int32_t* a1, const int32_t* a2, const int32_t* a3, const double* w6) {
+    NEED_CTX(); return guard(ctx, [&] { ctx->e->set_virtual_sites(n, type, site, a1, a2, a3, w6); });
+}
+int32_t mhip_place_virtual_sites(mhip_ctx* ctx) { NEED_CTX(); return guard(ctx, [&] { ctx->e->place_virtual_sites(); }); }
+int32_t mhip_distribute_forces(mhip_ctx* ctx, void* f, int32_t mk) { NEED_CTX(); return guard(ctx, [&] { if (!f) throw mhip::ApiError{MHIP_ERR_INVALID, "null force buffer"}; ctx->e->distribute_forces(f, mk); }); }
+int32_t mhip_virtual_site_info(mhip_ctx* ctx, int64_t* out8) { NEED_CTX(); return guard(ctx, [&] { if (!out8) throw mhip::ApiError{MHIP_ERR_INVALID, "null output"}; ctx->e->virtual_site_info(out8); }); }
 int32_t mhip_domain_info(mhip_ctx* ctx, int64_t* out8) { NEED_CTX(); return guard(ctx, [&] { if (!out8) throw mhip::ApiError{MHIP_ERR_INVALID, "null output"}; ctx->e->domain_info(out8); }); }
 int32_t mhip_domain_export(mhip_ctx* ctx, int64_t* gid_dev, void* par4_dev) { NEED_CTX(); return guard(ctx, [&] { ctx->e->domain_export(gid_dev, par4_dev); }); }
 int32_t mhip_vv_halo_begin(mhip_ctx* ctx, double dt, const int32_t* idx, const void* shift, int64_t n, void* out) { NEED_CTX(); return guard(ctx, [&] { ctx->e->halo_begin(dt, idx, shift, n, out); }); }

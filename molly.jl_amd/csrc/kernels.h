@@ -2292,11 +2292,13 @@ __global__ void k_vcm_from_total(const double* __restrict__ total4, T* vcm) {
 }
 
 template <class T>
-__global__ void k_shift_vel(int64_t n, typename Vec<T>::T4* vel, const T* __restrict__ vcm, const double* __restrict__ cm_part, int n_cm_part) {
+__global__ void k_shift_vel(int64_t n, typename Vec<T>::T4* vel, const T* __restrict__ vcm, const double* __restrict__ cm_part, int n_cm_part,
+                            const int32_t* __restrict__ orig, const uint8_t* __restrict__ skip) {      // skip (nullable): per caller index, atoms left alone (virtual sites)
     T vc[3];
     if (cm_part) block_vcm<T>(cm_part, n_cm_part, vc);
     else { vc[0] = vcm[0]; vc[1] = vcm[1]; vc[2] = vcm[2]; }
     for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
+        if (orig && skip[orig[s]]) continue;
         auto v = vel[s]; v.x -= vc[0]; v.y -= vc[1]; v.z -= vc[2]; vel[s] = v;
     }
 }

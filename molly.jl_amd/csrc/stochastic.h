@@ -28,9 +28,10 @@ void launch_langevin(hipStream_t s, int n_blocks, int64_t n, typename Vec<T>::T4
                      const int32_t* orig, const StochP<T>& P, const T* vcm, const double* cm_in, int n_cm_in, double* cm_out, const GridP<T>& G,
                      const typename Vec<T>::T4* frc_add = nullptr);      // frc_add (nullable): a second force array added on the way (a small system's bonded sums)
 // mode 0: Andersen re-draws (probability prob_u64 / 2⁶⁴ per atom); mode 1: every atom gets a Maxwell-Boltzmann velocity
+// site (nullable): per caller index, the virtual sites — left alone by mode 0 and by the pending CM removal, set to zero by mode 1
 template <class T>
 void launch_redraw(hipStream_t s, int mode, int64_t n, typename Vec<T>::T4* vel, const int32_t* orig, const StochP<T>& P,
-                   const T* vcm, const double* cm_in, int n_cm_in);
+                   const T* vcm, const double* cm_in, int n_cm_in, const uint8_t* site = nullptr);
 // test hook: the raw generator, out[4] = philox4x32_10(ctr, key) on the device
 // the same generator on the host: per-step (key, ctr1) pairs of a thermostat are drawn from a stream keyed by the user's seed
 void philox_host(uint64_t ctr0, uint64_t ctr1, uint64_t key, uint32_t* out4);

@@ -44,13 +44,17 @@ __global__ void __launch_bounds__(256) k_langevin(int64_t n, typename Vec<T>::T4
 // MODE 1 (random_velocities!): velocity from block ctr0 (kernels.jl:695-699).  A pending CM removal is applied on the way.
 template <class T, int MODE>
 __global__ void __launch_bounds__(256) k_redraw(int64_t n, typename Vec<T>::T4* vel, const int32_t* __restrict__ orig, StochP<T> P,
-                                                const T* __restrict__ vcm, const double* __restrict__ cm_in, int n_cm_in) {
+                                                const T* __restrict__ vcm, const double* __restrict__ cm_in, int n_cm_in, const uint8_t* __restrict__ site) {
     T vc[3] = {T(0), T(0), T(0)};
     const bool sub = vcm != nullptr || cm_in != nullptr;
     if (cm_in) block_vcm<T>(cm_in, n_cm_in, vc);
     else if (vcm) { vc[0] = vcm[0]; vc[1] = vcm[1]; vc[2] = vcm[2]; }
     for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
         auto v = vel[s];
+        if (site && site[orig[s]]) {      // a virtual site (per caller index): random_velocities! zeroes it (spatial.jl:823-831), the thermostat and the CM removal leave it alone (coupling.jl:209)
+            if constexpr (MODE == 1) { v.x = v.y = v.z = T(0); vel[s] = v; }
+            continue;
+        }
         if (sub) { v.x -= vc[0]; v.y -= vc[1]; v.z -= vc[2]; }
         uint64_t ctr0 = (uint64_t)orig[s] + 1;
         bool draw = true;
@@ -85,10 +89,10 @@ void launch_langevin(hipStream_t s, int n_blocks, int64_t n, typename Vec<T>::T4
 }
 template <class T>
 void launch_redraw(hipStream_t s, int mode, int64_t n, typename Vec<T>::T4* vel, const int32_t* orig, const StochP<T>& P,
-                   const T* vcm, const double* cm_in, int n_cm_in) {
+                   const T* vcm, const double* cm_in, int n_cm_in, const uint8_t* site) {
     const int nb = (int)std::min<int64_t>((n + 255) / 256, 1024);
-    if (mode == 0) hipLaunchKernelGGL((k_redraw<T, 0>), dim3(nb), dim3(256), 0, s, n, vel, orig, P, vcm, cm_in, n_cm_in);
-    else hipLaunchKernelGGL((k_redraw<T, 1>), dim3(nb), dim3(256), 0, s, n, vel, orig, P, vcm, cm_in, n_cm_in);
+    if (mode == 0) hipLaunchKernelGGL((k_redraw<T, 0>), dim3(nb), dim3(256), 0, s, n, vel, orig, P, vcm, cm_in, n_cm_in, site);
+    else hipLaunchKernelGGL((k_redraw<T, 1>), dim3(nb), dim3(256), 0, s, n, vel, orig, P, vcm, cm_in, n_cm_in, site);
 }
 void philox_host(uint64_t ctr0, uint64_t ctr1, uint64_t key, uint32_t* out4) {
     const U4 r = philox_u64(ctr0, ctr1, key);
@@ -98,7 +102,7 @@ void launch_philox_probe(hipStream_t s, const uint32_t* in, uint32_t* out) { hip
 
 template void launch_langevin<float>(hipStream_t, int, int64_t, float4*, float4*, const float4*, const int32_t*, const StochP<float>&, const float*, const double*, int, double*, const GridP<float>&, const float4*);
 template void launch_langevin<double>(hipStream_t, int, int64_t, double4*, double4*, const double4*, const int32_t*, const StochP<double>&, const double*, const double*, int, double*, const GridP<double>&, const double4*);
-template void launch_redraw<float>(hipStream_t, int, int64_t, float4*, const int32_t*, const StochP<float>&, const float*, const double*, int);
-template void launch_redraw<double>(hipStream_t, int, int64_t, double4*, const int32_t*, const StochP<double>&, const double*, const double*, int);
+template void launch_redraw<float>(hipStream_t, int, int64_t, float4*, const int32_t*, const StochP<float>&, const float*, const double*, int, const uint8_t*);
+template void launch_redraw<double>(hipStream_t, int, int64_t, double4*, const int32_t*, const StochP<double>&, const double*, const double*, int, const uint8_t*);
 
 }  // namespace mhip

@@ -18,7 +18,7 @@ def pme_mesh(box, alpha, error_tol=0.0005):
 class Case:
     def __init__(self, coords, box, lj=None, coul=None, r_list=math.inf, rebuild_every=10, velocities=None, charge=None,
                  sigma=None, eps=None, mass=None, excluded=None, special=None, bonds=None, angles=None, torsions=None,
-                 ewald_excl=None, name="case", pme=None, triclinic=None, lam=None, constraints=None):
+                 ewald_excl=None, name="case", pme=None, triclinic=None, lam=None, constraints=None, virtual_sites=()):
         """lj: None | dict(cutoff=(kind, rc[, ra]), weight_special=1.0)
         coul: None | dict(kind="plain"|"rf"|"ewald", cutoff=(kind, rc[, ra]) (plain), rc=…, eps_rf=78.3, tol=5e-4,
                           approx=True, weight_special=1.0)"""
@@ -35,6 +35,8 @@ class Case:
         self.name = name
         self.triclinic = triclinic   # None | dict(basis=3x3, approx_images=True): TriclinicBoundary; `box` = the basis' diagonal
         self.constraints = constraints   # None | dict(dist=dict(i, j, d), angle=dict(i, j, k, theta, d_ij, d_jk), dist_tolerance=…, max_iters=…): SHAKE_RATTLE
+        # () | tuples (type, atom_ind, atom_1, atom_2, atom_3, weight_1, weight_2, weight_3, weight_12, weight_13, weight_cross), 0-based (−1: unused): VirtualSite
+        self.virtual_sites = tuple(tuple(v) for v in virtual_sites)
         self.pme = pme       # None | dict(order=5, error_tol=5e-4, eps_r=1.0[, mesh=(nx, ny, nz)]): general interaction PME (needs coul kind "ewald")
 
     def pme_params(self, dtype):
@@ -126,7 +128,8 @@ class Case:
         return m.System(coords=self.coords if coords is None else coords, boundary=boundary,
                         velocities=self.velocities if velocities is None else velocities, pairwise_inters=tuple(inters),
                         specific_inter_lists=tuple(sils), neighbor_finder=nf, dtype=dtype, charge=self.charge,
-                        sigma=self.sigma, eps=self.eps, mass=self.mass, general_inters=tuple(gis), lam=self.lam, constraints=cons)
+                        sigma=self.sigma, eps=self.eps, mass=self.mass, general_inters=tuple(gis), lam=self.lam, constraints=cons,
+                        **(dict(virtual_sites=tuple(m.VirtualSite(*v) for v in self.virtual_sites)) if self.virtual_sites else {}))
 
 
 # ---- SURVEY §8(d) synthetic LJ fluid (argon at 1400 kg/m³, benchmark/benchmark_gpu_tiles.jl:18-25) ------
