@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "owners.h"
 #include "physics.h"
 
 namespace mhip {
@@ -266,23 +267,13 @@ __global__ void k_bonded_collect(int64_t n_owned, const int32_t* __restrict__ or
     bonded_collect_lane<T, false>(blockIdx.x * (int64_t)blockDim.x + threadIdx.x, n_owned, orig, role_start, role_slot, slots, frc, parts, n_parts, part_stride);
 }
 
-template <class U> struct HBuf {   // device array filled from a host array once
-    U* p = nullptr; size_t n = 0;
-    void set(const U* h, size_t m) {
-        if (p) (void)hipFree(p);
-        p = nullptr; n = m;
-        if (m) { MHIP_HIP(hipMalloc((void**)&p, m * sizeof(U))); MHIP_HIP(hipMemcpy(p, h, m * sizeof(U), hipMemcpyHostToDevice)); }
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-
 template <class T> struct Bonded {
     using T4 = typename Vec<T>::T4;
-    HBuf<int32_t> b_i, b_j, a_i, a_j, a_k, t_i, t_j, t_k, t_l, t_per, x_i, x_j;
-    HBuf<T> b_k, b_r0, a_kth, a_th0, t_phase, t_k0;
+    DBuf<int32_t> b_i, b_j, a_i, a_j, a_k, t_i, t_j, t_k, t_l, t_per, x_i, x_j;
+    DBuf<T> b_k, b_r0, a_kth, a_th0, t_phase, t_k0;
     // slot path: per-atom CSR of slot indices (rebuilt lazily after any set_*), slot array
-    std::vector<int32_t> h_idx[4][4]; HBuf<int32_t> role_start, role_slot; bool roles_dirty = true; int64_t roles_cap = 0, n_slots = 0, slot_base[4] = {0, 0, 0, 0};
-    T4* slots = nullptr; size_t slots_cap = 0;
+    std::vector<int32_t> h_idx[4][4]; DBuf<int32_t> role_start, role_slot; bool roles_dirty = true; int64_t roles_cap = 0, n_slots = 0, slot_base[4] = {0, 0, 0, 0};
+    DBuf<T4> slots;
     void keep(int type, int64_t n, std::initializer_list<const int32_t*> idx) {
         int r = 0; for (const int32_t* a : idx) { h_idx[type][r].assign(a, a + n); ++r; }
         for (; r < 4; ++r) h_idx[type][r].clear();
@@ -305,7 +296,7 @@ template <class T> struct Bonded {
         role_start.set(start.data(), start.size());
         if (list.empty()) list.push_back(0);
         role_slot.set(list.data(), list.size());
-        if ((size_t)n_slots > slots_cap) { if (slots) (void)hipFree(slots); slots = nullptr; slots_cap = (size_t)n_slots; MHIP_HIP(hipMalloc((void**)&slots, slots_cap * sizeof(T4))); }
+        slots.reserve((size_t)n_slots);
         roles_dirty = false; roles_cap = cap;
     }
 
@@ -323,7 +314,6 @@ template <class T> struct Bonded {
     void set_ewx(int64_t cap, int64_t n, const int32_t* i, const int32_t* j) { check(cap, n, {i, j}); x_i.set(i, n); x_j.set(j, n); keep(3, n, {i, j}); }
     void on_reorder() {}   // terms address atoms through inv[]: nothing to rebuild after a re-sort
     bool any() const { return b_i.n || a_i.n || t_i.n || x_i.n; }
-    void release() { for (auto* h : {&b_i, &b_j, &a_i, &a_j, &a_k, &t_i, &t_j, &t_k, &t_l, &t_per, &x_i, &x_j}) h->release(); for (auto* h : {&b_k, &b_r0, &a_kth, &a_th0, &t_phase, &t_k0}) h->release(); role_start.release(); role_slot.release(); if (slots) (void)hipFree(slots); slots = nullptr; slots_cap = 0; }
 
     static constexpr int BT = 64;   // one wave per block: thousands of short, latency-bound terms spread over all CUs
     BondedArgs<T> args(const GridP<T>& G, const InterP<T>& I, const T4* pos, const int32_t* inv, T4* frc, double* part) const {
@@ -340,7 +330,7 @@ template <class T> struct Bonded {
     int n_blocks() const { return cdiv(b_i.n, BT) + cdiv(a_i.n, BT) + cdiv(t_i.n, BT) + cdiv(x_i.n, BT); }
     // the slot path's tables for the current capacity (rebuilt after any set_*); args for the term kernel writing into the slots
     void ensure_roles(hipStream_t s, int64_t cap) { if (roles_dirty || roles_cap != cap) { MHIP_HIP(hipStreamSynchronize(s)); build_roles(cap); } }
-    BondedArgs<T> slot_args(const GridP<T>& G, const InterP<T>& I, const T4* pos, const int32_t* inv) const { return args(G, I, pos, inv, slots, nullptr); }
+    BondedArgs<T> slot_args(const GridP<T>& G, const InterP<T>& I, const T4* pos, const int32_t* inv) const { return args(G, I, pos, inv, slots.p, nullptr); }
 
     // forces ADDED to frc (sorted order; `orig` = sorted→caller map of the n_owned owned atoms, `cap` = context capacity).
     // (no atomics: a one-launch scatter with float atomics measured 2x slower and is not bit-reproducible)
@@ -349,8 +339,8 @@ template <class T> struct Bonded {
         int nb = n_blocks();
         if (!nb) return;
         if (roles_dirty || roles_cap != cap) { MHIP_HIP(hipStreamSynchronize(s)); build_roles(cap); }
-        if (!terms_done) hipLaunchKernelGGL((k_bonded<T, false, true>), dim3(nb), dim3(BT), 0, s, args(G, I, pos, inv, slots, nullptr));
-        hipLaunchKernelGGL(k_bonded_collect<T>, dim3((unsigned)cdiv(n_owned * COLLECT_LANES, (int64_t)256)), dim3(256), 0, s, n_owned, orig, (const int32_t*)role_start.p, (const int32_t*)role_slot.p, (const T4*)slots, frc,
+        if (!terms_done) hipLaunchKernelGGL((k_bonded<T, false, true>), dim3(nb), dim3(BT), 0, s, args(G, I, pos, inv, slots.p, nullptr));
+        hipLaunchKernelGGL(k_bonded_collect<T>, dim3((unsigned)cdiv(n_owned * COLLECT_LANES, (int64_t)256)), dim3(256), 0, s, n_owned, orig, (const int32_t*)role_start.p, (const int32_t*)role_slot.p, (const T4*)slots.p, frc,
                            fold_parts, fold_n, fold_stride);
         fold_parts = nullptr; fold_n = 0;
         MHIP_HIP(hipGetLastError());

@@ -30,12 +30,6 @@ namespace mhip {
 
 static thread_local std::string g_create_error;
 
-template <class U> struct DBuf {
-    U* p = nullptr; size_t n = 0;
-    void reserve(size_t m) { if (m > n) { if (p) (void)hipFree(p); p = nullptr; MHIP_HIP(hipMalloc((void**)&p, std::max<size_t>(m, 1) * sizeof(U))); n = m; } }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-
 struct EngineBase {
     std::string err;
     virtual ~EngineBase() {}
@@ -120,13 +114,13 @@ struct EngineBase {
 struct Prof {
     static constexpr int NS = 8;
     bool on = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[NS];
+    std::vector<std::pair<Event, Event>> ev[NS];
     size_t used[NS] = {};
     double ms[NS] = {};
     int64_t calls[NS] = {};
     void begin(int st, hipStream_t s) {
         if (!on) return;
-        if (used[st] == ev[st].size()) { hipEvent_t a, b; MHIP_HIP(hipEventCreate(&a)); MHIP_HIP(hipEventCreate(&b)); ev[st].push_back({a, b}); }
+        if (used[st] == ev[st].size()) add(st);
         MHIP_HIP(hipEventRecord(ev[st][used[st]].first, s));
     }
     void end(int st, hipStream_t s) {
@@ -144,8 +138,8 @@ struct Prof {
     void reset() { for (int st = 0; st < NS; ++st) { used[st] = 0; ms[st] = 0; calls[st] = 0; } }
     // events for the first launches are made before the pass that uses them: creating two per launch on the way (≈ 10 µs each on the
     // host) let the stream run dry between a begin event and its kernel, and the gap counted as kernel time
-    void reserve(int st, size_t n) { while (ev[st].size() < n) { hipEvent_t a, b; MHIP_HIP(hipEventCreate(&a)); MHIP_HIP(hipEventCreate(&b)); ev[st].push_back({a, b}); } }
-    void release() { for (int st = 0; st < NS; ++st) { for (auto& e : ev[st]) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } ev[st].clear(); } }
+    void reserve(int st, size_t n) { while (ev[st].size() < n) add(st); }
+    void add(int st) { Event a, b; a.make(); b.make(); ev[st].emplace_back(std::move(a), std::move(b)); }
 };
 
 static int env_int(const char* name, int dflt) { const char* v = std::getenv(name); return v && *v ? std::atoi(v) : dflt; }
@@ -160,7 +154,7 @@ template <class T> class Engine final : public EngineBase {
     InterP<T> I;
     int ljm = LJ_OFF, coulm = MHIP_COUL_NONE;
     int64_t cap, n_owned, n_ghost, n_tot;
-    hipStream_t stream = nullptr; bool own_stream = false;
+    Stream stream;   // declared before every buffer: destroyed after all of them
     int device = 0;
 
     // per-atom state in sorted order, double-buffered for the re-sort
@@ -230,10 +224,10 @@ template <class T> class Engine final : public EngineBase {
     // single list, same idea: a rebuild step whose displacement check shows the list still covers every cutoff sphere is skipped
     bool lazy_single = false; int64_t n_skipped = 0;
     bool dual = false, dual_disabled = false, margin_zero = false, want_margin_zero = false; int margin_halvings = 0; int early_outer = 0; double outer_margin = 0; int64_t last_outer_step = 0, n_outer = 0, n_filters = 0; T r_in = 0, r_in2 = 0;
-    DBuf<int32_t> flags; int32_t* h_flags = nullptr;
+    DBuf<int32_t> flags; Pinned<int32_t> h_flags;
     int64_t total_rows = 0, outer_rows = 0;      // rows (of four entries per lane, per wave) of the list the plain passes walk | of the outer list as searched
     // reductions
-    DBuf<double> red_part, red_out, cm_step; double* h_red = nullptr; DBuf<T> vcm;
+    DBuf<double> red_part, red_out, cm_step; Pinned<double> h_red; DBuf<T> vcm;
     // the Σ m v removal deferred to the next consumer of the velocities: none, subtract vcm, or re-sum n per-block partials {ΣPx, ΣPy, ΣPz, ΣM} at an address
     class PendingCm {
         int mode_ = 0; const double* parts_ = nullptr;
@@ -284,13 +278,12 @@ template <class T> class Engine final : public EngineBase {
         device = c.device_id;
         if (device < 0 || device >= ndev) throw ApiError{MHIP_ERR_INVALID, "device_id out of range"};
         MHIP_HIP(hipSetDevice(device));
-        MHIP_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); own_stream = true;
+        stream.create(hipStreamNonBlocking);
         setup_inter(); setup_grid();
         for (int k = 0; k < 2; ++k) { pos[k].reserve(cap); vel[k].reserve(cap); frc[k].reserve(cap); lj[k].reserve(cap); orig[k].reserve(cap); }
         inv.reserve(cap); key_in.reserve(cap); key_out.reserve(cap); idx_in.reserve(cap); perm.reserve(cap);
         flags.reserve(N_FLAGS); red_out.reserve(8); vcm.reserve(4); cm_step.reserve(2 * 4 * 1024);   // two halves: k_vv_mid reads one while it writes the other
-        MHIP_HIP(hipHostMalloc((void**)&h_flags, N_FLAGS * sizeof(int32_t)));
-        MHIP_HIP(hipHostMalloc((void**)&h_red, 8 * sizeof(double)));
+        h_flags.make(N_FLAGS); h_red.make(8);
         for (int k = 0; k < 2; ++k) { MHIP_HIP(hipMemsetAsync(pos[k].p, 0, cap * sizeof(T4), stream)); MHIP_HIP(hipMemsetAsync(vel[k].p, 0, cap * sizeof(T4), stream)); MHIP_HIP(hipMemsetAsync(frc[k].p, 0, cap * sizeof(T4), stream)); MHIP_HIP(hipMemsetAsync(lj[k].p, 0, cap * sizeof(T2), stream)); }
         std::vector<int32_t> iota(cap); for (int64_t i = 0; i < cap; ++i) iota[i] = (int32_t)i;
         MHIP_HIP(hipMemcpyAsync(orig[0].p, iota.data(), cap * sizeof(int32_t), hipMemcpyHostToDevice, stream));
@@ -301,27 +294,9 @@ template <class T> class Engine final : public EngineBase {
         cub_tmp.reserve(std::max(tb, tb2) + 256);
         choose_blocking();
     }
-    ~Engine() override {
+    ~Engine() override {      // the members give back what they own, the stream last (it is declared first)
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
-        for (int k = 0; k < 2; ++k) { pos[k].release(); vel[k].release(); frc[k].release(); lj[k].release(); orig[k].release(); }
-        inv.release(); key_in.release(); key_out.release(); cell_rank.release(); idx_in.release(); perm.release(); cell_cnt.release(); cell_start.release(); cub_tmp.release();
-        pos_snap_in.release(); cnt_in.release(); cnt_outer.release();
-        nbr_gs.release(); rows_gs.release(); frc_parts.release(); wave_rows_in.release(); nbr_in.release(); pos_snap.release(); blk_disp2.release(); tile_idx_in.release(); tile_cnt_in.release(); rows_x.release(); nbr_x.release(); tile_idx_x.release(); tile_cnt_x.release(); blk_ghost.release(); blk_ghost_in.release();
-        xl_start.release(); xl_list.release(); tile_idx.release(); tile_cnt.release(); wave_rows.release(); nbr.release(); blk_center.release();
-        flags.release(); red_part.release(); red_out.release(); cm_step.release(); vcm.release(); stage_a.release(); stage_b.release(); stage_i.release(); bonded.release(); pme.release(); frc_scratch.release(); nl_counter.release(); state_changed.release(); pos_alt.release(); cm_blk.release(); cm_pub.release();
-        xf_release(); dom_release(); hx.release();
-        prof.release();
-        frc_side.release();
-        if (h_flags) (void)hipHostFree(h_flags);
-        if (h_trk) (void)hipHostFree(h_trk);
-        if (ev_trk) (void)hipEventDestroy(ev_trk);
-        if (h_prune) (void)hipHostFree(h_prune);
-        if (ev_prune) (void)hipEventDestroy(ev_prune);
-        if (h_red) (void)hipHostFree(h_red);
-        if (h_con) (void)hipHostFree(h_con);
-        con_atoms.release(); con_d.release(); con_stat.release(); vs_item.release(); vs_hrec.release(); vs_hw.release(); vs_rec.release(); vs_w.release(); vs_flag.release();
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
 
   private:
@@ -496,8 +471,7 @@ template <class T> class Engine final : public EngineBase {
         static const int cand[][2] = {{256, 4}, {256, 2}, {128, 8}, {128, 4}, {128, 2}, {64, 16}, {64, 8}};
         flush_cm();
         const int64_t step = last_build_step == std::numeric_limits<int64_t>::min() ? 0 : last_build_step;
-        hipEvent_t e0, e1;
-        MHIP_HIP(hipEventCreate(&e0)); MHIP_HIP(hipEventCreate(&e1));
+        Event e0, e1; e0.make(); e1.make();
         int n = 0, best_bi = 0, best_js = 0; float best = 0;
         for (auto& c : cand) {
             if (c[0] * c[1] > MAX_THREADS || (int64_t)c[0] > std::max<int64_t>(n_owned, 64)) continue;
@@ -519,13 +493,12 @@ template <class T> class Engine final : public EngineBase {
                 float ms = 0; MHIP_HIP(hipEventElapsedTime(&ms, e0, e1));
                 us = ms * 1000.f / (float)n_passes;
             } catch (const ApiError& err) {
-                if (err.code != MHIP_ERR_CAPACITY) { user_bi = user_js = 0; (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); throw; }
+                if (err.code != MHIP_ERR_CAPACITY) { user_bi = user_js = 0; throw; }
             }
             if (n < max_trials && trials) { trials[n].block_atoms = us < 0 ? c[0] : BI; trials[n].j_split = us < 0 ? c[1] : JS; trials[n].us_per_pass = us; }
             ++n;
             if (us > 0 && (best_bi == 0 || us < best)) { best = us; best_bi = BI; best_js = JS; }
         }
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
         user_bi = best_bi; user_js = best_js;                  // (0, 0 = automatic, when nothing could be timed)
         reblock(); frc_valid = false;
         return n;
@@ -794,7 +767,7 @@ template <class T> class Engine final : public EngineBase {
     // previous decision's horizon (it reached up to the check step), a prune or a search that the measurement asks for happens at
     // s + 1 (with that step of headroom in the outer-list test).  (Taking the maxima inside k_forces instead cost its packed loop
     // 14 % through a different register assignment, with the same instructions: measured, dropped.)
-    DBuf<float> trk_part, trk_out; float* h_trk = nullptr; hipEvent_t ev_trk = nullptr;
+    DBuf<float> trk_part, trk_out; Pinned<float> h_trk; Event ev_trk;
     bool trk_issued = false; int64_t trk_step = -1, trk_prune_id = -1, trk_outer_id = -1; double trk_prev_vmax = 0;   // (ids: the running counts of prunes / outer searches)
     bool in_vv_fused = false;      // inside the fused step loop of vv_loop (async_ok and the pair pass's Σ m v summing read it)
     bool in_lang_fused = false;      // inside mhip_langevin_run of a small system whose last force launch integrates (the pair launch's extra workgroup then sums the Σ m v partials, as inside mhip_vv_run)
@@ -804,8 +777,7 @@ template <class T> class Engine final : public EngineBase {
     void trk_reserve(int n_parts) { trk_part.reserve(3 * (size_t)std::max(n_parts, 1024)); trk_out.reserve(4); }
     // the check of `step` from the n_parts per-block maxima in trk_part: reduce, copy, event
     void issue_track(int n_parts, int64_t step) {
-        if (!h_trk) MHIP_HIP(hipHostMalloc((void**)&h_trk, 4 * sizeof(float)));
-        if (!ev_trk) MHIP_HIP(hipEventCreateWithFlags(&ev_trk, hipEventDisableTiming));
+        h_trk.make(4); ev_trk.make(hipEventDisableTiming);
         hipLaunchKernelGGL(k_track_reduce, dim3(1), dim3(256), 0, stream, n_parts, (const float*)trk_part.p, trk_out.p, h_trk);   // (straight into pinned host memory)
         MHIP_HIP(hipEventRecord(ev_trk, stream));
         trk_issued = true; trk_step = step; trk_prev_vmax = last_vmax; trk_prune_id = n_filters; trk_outer_id = n_outer;
@@ -932,7 +904,7 @@ template <class T> class Engine final : public EngineBase {
     // idled while its host woke up and queued the rest of the step): the summary kernel writes into pinned words of their own behind an event; until the host finds the
     // event complete the next passes are shaped for the OUTER list's largest tile (a pruned tile is a subset of it: same results, a larger LDS carve-up for a step or
     // two), and a displacement beyond the ghost margin — which fails the run on this path anyway (after_forces) — is reported when it is read, a step or two later.
-    int32_t* h_prune = nullptr; hipEvent_t ev_prune = nullptr; bool prune_pending = false; int64_t prune_pending_id = -1;
+    Pinned<int32_t> h_prune; Event ev_prune; bool prune_pending = false; int64_t prune_pending_id = -1;
     void prune_resolve(bool block) {
         if (!prune_pending) return;
         if (!block && hipEventQuery(ev_prune) != hipSuccess) { (void)hipGetLastError(); return; }
@@ -1126,12 +1098,12 @@ template <class T> class Engine final : public EngineBase {
                     // Several ranks on ONE device: the peers need the same compute units to produce what this launch would wait for, and a grid of resident,
                     // spinning workgroups can leave their kernels no room (a search kernel's 100 KB of LDS next to two spinning blocks per unit: a 2 s stall,
                     // then the time-out).  A one-workgroup launch waits instead; the pass behind it finds every word in place.
-                    XferWait W{}; W.mine = reinterpret_cast<const XferHeader*>(xf.region); W.parity = (int)(xf.seq & 1u); W.seq = xf.seq; W.peers = xf.d_peers.p; W.n_peers = xf.n_peers; W.err = xf.err.p; W.ticks = xf_ticks();
+                    XferWait W{}; W.mine = reinterpret_cast<const XferHeader*>(xf.region.p); W.parity = (int)(xf.seq & 1u); W.seq = xf.seq; W.peers = xf.d_peers.p; W.n_peers = xf.n_peers; W.err = xf.err.p; W.ticks = xf_ticks();
                     hipLaunchKernelGGL(k_xfer_wait_all, dim3(1), dim3(64), 0, stream, W);
                 }
                 launch_forces_uniform_f32(A, false, false, lds_force, (unsigned)(BI * JS), stream, true, req.halo, req.lang != nullptr);
                 if (req.halo) ++xf.seq;      // (the launch's last wave announces exchange xf.seq at the peers)
-                std::swap(pos[cur].p, pos_alt.p); std::swap(pos[cur].n, pos_alt.n);      // the epilogues wrote the drifted coordinates into the other buffer: it is the current one now
+                std::swap(pos[cur], pos_alt);      // the epilogues wrote the drifted coordinates into the other buffer: it is the current one now
                 res.step = true; res.parts = n_blocks; ++n_fused_steps;
             } else launch_forces_any(A, energy);
         } else launch_forces_any(A, energy);
@@ -1155,7 +1127,7 @@ template <class T> class Engine final : public EngineBase {
         if (prune) {   // validity of the pruned list: nobody moved more than half the margin since the outer search
             // one single-block launch that leaves its figures in pinned host memory (no zeroing launch, no copy launch) …
             const bool late = xf_direct && n_ghost > 0 && prune_late_env;      // inside mhip_domain_run on a ghosted sub-domain: read behind an event (prune_resolve)
-            if (late && !h_prune) { MHIP_HIP(hipHostMalloc((void**)&h_prune, N_FLAGS * sizeof(int32_t))); MHIP_HIP(hipEventCreateWithFlags(&ev_prune, hipEventDisableTiming)); }
+            if (late) { h_prune.make(N_FLAGS); ev_prune.make(hipEventDisableTiming); }
             int32_t* const h_dst = late ? h_prune : h_flags;
             hipLaunchKernelGGL(k_prune_summary, dim3(1), dim3(1024), 0, stream, n_blocks, n_blocks * JS * (BI / WAVE), n_blocks * (BI / WAVE), R_cap,
                                (const int32_t*)tile_cnt_in.p, wave_rows_in.p, (const float*)blk_disp2.p, flags.p, h_dst);
@@ -1211,7 +1183,6 @@ template <class T> class Engine final : public EngineBase {
         bool plan_ok = false, tile_ok = false;      // per ghost plan + sort | per prune
         int64_t trk_step = -1;                      // the step whose coordinates the last fused launch measured against the snapshots (trk_part), −1: none
         int64_t n_steps = 0;
-        void release() { order.release(); flags.release(); tsrc.release(); ghost_row.release(); cm_row.release(); snd_start.release(); snd_cnt.release(); blk_send.release(); snd.release(); cm_dst.release(); ann.release(); }
     } hx;
     static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
     void hx_build() {
@@ -1261,7 +1232,7 @@ template <class T> class Engine final : public EngineBase {
             HaloStep& H = A.H;
             const int par = (int)(xf.seq & 1u);
             H.order = hx.order.p; H.flags = hx.flags.p; H.tsrc = hx.tsrc.p;
-            H.rows = xf_rows(par); H.seq_in = reinterpret_cast<const XferHeader*>(xf.region)->seq_in[par];
+            H.rows = xf_rows(par); H.seq_in = reinterpret_cast<const XferHeader*>(xf.region.p)->seq_in[par];
             H.peers = xf.d_peers.p; H.n_peers = xf.n_peers; H.seq_wait = xf.seq; H.err = xf.err.p; H.ticks = xf_ticks();
             H.snd_start = hx.snd_start.p; H.snd = hx.snd.p; H.half_stride = (int64_t)xf.rows_cap * 3;
             H.parity_send = (int)((xf.seq + 1u) & 1u); H.seq_send = xf.seq + 1u;
@@ -1469,8 +1440,7 @@ template <class T> class Engine final : public EngineBase {
     // ---------------------------------------------------------------------------------------------
     void set_stream(void* s) override {
         MHIP_HIP(hipStreamSynchronize(stream));
-        if (own_stream) { (void)hipStreamDestroy(stream); own_stream = false; }
-        stream = (hipStream_t)s;
+        stream.use((hipStream_t)s);
     }
     void synchronize() override { MHIP_HIP(hipStreamSynchronize(stream)); }
     void set_profiling(bool on) override {
@@ -1524,7 +1494,6 @@ template <class T> class Engine final : public EngineBase {
         }
         if (want_eshift() != eshift) stale = true;   // the lists in use are in the other entry format
         pc_valid = false;   // Σq, Σq² of the PME self / net-charge terms are read back only when an energy asks for them
-        s3.release(); s4.release(); s5.release();
         params_set = true; frc_valid = false; vs_mass_ok = false;
     }
 
@@ -2070,7 +2039,7 @@ template <class T> class Engine final : public EngineBase {
             if (!(xf_direct && xf.n_peers > 0) && !hp.recv) throw ApiError{MHIP_ERR_STATE, "the current ghost plan was made inside the engine (mhip_set_domain) and has no receive buffer: step it with mhip_domain_run, or hand a plan with buffers to mhip_set_halo_plan"};
             tr("k_halo_unpack");
             XferWait W{};    // inside mhip_domain_run with peers: wait for exchange xf.seq, read my region's half
-            if (xf_direct && xf.n_peers > 0) { W.mine = reinterpret_cast<const XferHeader*>(xf.region); W.parity = (int)(xf.seq & 1u); W.seq = xf.seq; W.peers = xf.d_peers.p; W.n_peers = xf.n_peers; W.err = xf.err.p; W.ticks = xf_ticks(); }
+            if (xf_direct && xf.n_peers > 0) { W.mine = reinterpret_cast<const XferHeader*>(xf.region.p); W.parity = (int)(xf.seq & 1u); W.seq = xf.seq; W.peers = xf.d_peers.p; W.n_peers = xf.n_peers; W.err = xf.err.p; W.ticks = xf_ticks(); }
             hipLaunchKernelGGL(k_halo_unpack<T>, dim3(cdiv(hp.n_recv_rows, 256)), dim3(256), 0, stream, hp.n_recv_rows, W.n_peers > 0 ? (const T*)xf_rows(W.parity) : (const T*)hp.recv, hp.recv_dst, hp.first_ghost, (const int32_t*)inv.p,
                                pos[cur].p, cm_all.p, std::max(hp.cm_rows, 1), W);
         }
@@ -2106,70 +2075,67 @@ template <class T> class Engine final : public EngineBase {
     }
     // ---- the ghost exchange inside the engine (halo_xfer.h): peer stores into IPC-mapped receive regions, the step loop in C++ --------
     struct Xfer {
-        unsigned char* region = nullptr; int64_t rows_cap = 0; int world = 0, rank = 0;
-        XferPeers peers{}; bool opened[XFER_MAX_RANKS] = {}; int64_t peer_cap[XFER_MAX_RANKS] = {};   // peer_cap: rows per half of each peer's region (its header says)
+        DBuf<unsigned char, hipDeviceMallocFinegrained> region; int64_t rows_cap = 0; int world = 0, rank = 0;
+        XferPeers peers{}; IpcMapping opened[XFER_MAX_RANKS]; int64_t peer_cap[XFER_MAX_RANKS] = {};   // peer_cap: rows per half of each peer's region (its header says)
         bool routes = false; int n_peers = 0; std::vector<int32_t> peer_rank;
         uint64_t dev_key = 0; bool shared_device = false;      // some peer runs on THIS device (several ranks on one GPU: the test set-up)
         DBuf<int32_t> row_peer, row_dst, d_peers; DBuf<unsigned int> done; DBuf<int32_t> err; DBuf<float> mine3, red3;
         uint32_t seq = 0, plan_seq = 0;
-        float* h_red3 = nullptr; int32_t* h_err = nullptr; hipEvent_t ev_plan = nullptr;
+        Pinned<float> h_red3; Pinned<int32_t> h_err; Event ev_plan;
         bool plan_pending = false; int64_t plan_step = -1, next_check = -1, plan_prune_id = -1, plan_outer_id = -1;      // (ids: the running counts of prunes / outer searches when the check was issued)
         RpPlanPtrs plan{}; uint32_t rp_seq = 0;      // every rank's plan area; number of the last re-plan made inside the engine (replan.h)
     } xf;
     bool xf_direct = false;      // inside mhip_domain_run: k_halo_pack stores into the peers' regions, k_halo_unpack waits for theirs
-    T* xf_rows(int parity) const { return reinterpret_cast<T*>(xf.region + XFER_ROWS_OFF) + (size_t)parity * xf.rows_cap * 3; }
+    T* xf_rows(int parity) const { return reinterpret_cast<T*>(xf.region.p + XFER_ROWS_OFF) + (size_t)parity * xf.rows_cap * 3; }
+    // what the collective check (xf_issue_plan_check) writes and waits on: made once, with or without a region
+    void xf_plan_words() { xf.mine3.reserve(4); xf.h_red3.make(4); xf.ev_plan.make(hipEventDisableTiming); }
     void xf_release() {
-        for (int r = 0; r < XFER_MAX_RANKS; ++r) if (xf.opened[r] && xf.peers.region[r]) { (void)hipIpcCloseMemHandle(xf.peers.region[r]); xf.opened[r] = false; }
-        if (xf.region) (void)hipFree(xf.region);
-        xf.region = nullptr;
+        for (auto& m : xf.opened) m.reset();
+        xf.region.release();
         xf.row_peer.release(); xf.row_dst.release(); xf.d_peers.release(); xf.done.release(); xf.err.release(); xf.mine3.release(); xf.red3.release();
-        if (xf.h_red3) (void)hipHostFree(xf.h_red3); if (xf.h_err) (void)hipHostFree(xf.h_err); if (xf.ev_plan) (void)hipEventDestroy(xf.ev_plan);
-        xf.h_red3 = nullptr; xf.h_err = nullptr; xf.ev_plan = nullptr;
+        xf.h_red3.reset(); xf.h_err.reset(); xf.ev_plan.reset();
     }
     // this rank's receive region: two halves of rows_cap rows of 3 reals behind the header, fine-grained device memory (peers write it,
     // this device polls it); its IPC handle goes to every peer
     void halo_region(int64_t rows_cap, int32_t world, int32_t my_rank, void* handle_out) override {
         if (rows_cap <= 0 || world < 1 || world > XFER_MAX_RANKS || my_rank < 0 || my_rank >= world) throw ApiError{MHIP_ERR_INVALID, "halo region: rows / world / rank out of range"};
         MHIP_HIP(hipStreamSynchronize(stream));
-        if (!xf.region || xf.rows_cap < rows_cap || xf.world != world || xf.rank != my_rank) {
-            if (xf.region) xf_release();
+        if (!xf.region.p || xf.rows_cap < rows_cap || xf.world != world || xf.rank != my_rank) {
+            if (xf.region.p) xf_release();
             const size_t bytes = xfer_region_bytes<T>(rows_cap);      // header | two row halves | plan area (replan.h)
-            MHIP_HIP(hipExtMallocWithFlags((void**)&xf.region, bytes, hipDeviceMallocFinegrained));
-            MHIP_HIP(hipMemset(xf.region, 0, bytes));
-            MHIP_HIP(hipMemcpy(xf.region + offsetof(XferHeader, rows_cap), &rows_cap, sizeof(int64_t), hipMemcpyHostToDevice));
+            xf.region.alloc(bytes);
+            MHIP_HIP(hipMemset(xf.region.p, 0, bytes));
+            MHIP_HIP(hipMemcpy(xf.region.p + offsetof(XferHeader, rows_cap), &rows_cap, sizeof(int64_t), hipMemcpyHostToDevice));
             {
                 hipDeviceProp_t pr; MHIP_HIP(hipGetDeviceProperties(&pr, device));
                 xf.dev_key = (((uint64_t)(uint32_t)pr.pciDomainID << 32) | ((uint64_t)(uint32_t)pr.pciBusID << 16) | (uint64_t)(uint32_t)pr.pciDeviceID) + 1u;
-                MHIP_HIP(hipMemcpy(xf.region + offsetof(XferHeader, dev_key), &xf.dev_key, sizeof(uint64_t), hipMemcpyHostToDevice));
+                MHIP_HIP(hipMemcpy(xf.region.p + offsetof(XferHeader, dev_key), &xf.dev_key, sizeof(uint64_t), hipMemcpyHostToDevice));
                 xf.shared_device = false;
             }
             xf.rows_cap = rows_cap; xf.world = world; xf.rank = my_rank; xf.seq = 0; xf.plan_seq = 0; xf.routes = false;
             for (int r = 0; r < XFER_MAX_RANKS; ++r) xf.peers.region[r] = nullptr;
-            xf.peers.region[my_rank] = xf.region; xf.peer_cap[my_rank] = rows_cap;
+            xf.peers.region[my_rank] = xf.region.p; xf.peer_cap[my_rank] = rows_cap;
             for (int r = 0; r < XFER_MAX_RANKS; ++r) xf.plan.area[r] = nullptr;
-            xf.plan.area[my_rank] = xf.region + xfer_plan_off<T>(rows_cap);
-            xf.done.reserve(1); xf.err.reserve(4); xf.mine3.reserve(4); xf.red3.reserve(4);
+            xf.plan.area[my_rank] = xf.region.p + xfer_plan_off<T>(rows_cap);
+            xf.done.reserve(1); xf.err.reserve(4); xf.red3.reserve(4);
             MHIP_HIP(hipMemset(xf.done.p, 0, sizeof(unsigned int))); MHIP_HIP(hipMemset(xf.err.p, 0, 4 * sizeof(int32_t)));
-            if (!xf.h_red3) MHIP_HIP(hipHostMalloc((void**)&xf.h_red3, 4 * sizeof(float)));
-            if (!xf.h_err) MHIP_HIP(hipHostMalloc((void**)&xf.h_err, 4 * sizeof(int32_t)));
-            if (!xf.ev_plan) MHIP_HIP(hipEventCreateWithFlags(&xf.ev_plan, hipEventDisableTiming));
+            xf_plan_words(); xf.h_err.make(4);
         }
         if (handle_out) {
             hipIpcMemHandle_t h;
-            MHIP_HIP(hipIpcGetMemHandle(&h, xf.region));
+            MHIP_HIP(hipIpcGetMemHandle(&h, xf.region.p));
             static_assert(sizeof(hipIpcMemHandle_t) == MHIP_IPC_HANDLE_BYTES, "hipIpcMemHandle_t is 64 bytes");
             std::memcpy(handle_out, &h, sizeof(h));
         }
     }
     void halo_open_peer(int32_t rank, const void* handle) override {
-        if (!xf.region) throw ApiError{MHIP_ERR_STATE, "mhip_halo_region first"};
+        if (!xf.region.p) throw ApiError{MHIP_ERR_STATE, "mhip_halo_region first"};
         if (rank < 0 || rank >= xf.world || !handle) throw ApiError{MHIP_ERR_INVALID, "halo peer: rank out of range or null handle"};
         if (rank == xf.rank) return;
-        if (xf.opened[rank]) { (void)hipIpcCloseMemHandle(xf.peers.region[rank]); xf.opened[rank] = false; }
         hipIpcMemHandle_t h; std::memcpy(&h, handle, sizeof(h));
-        void* base = nullptr;
-        MHIP_HIP(hipIpcOpenMemHandle(&base, h, hipIpcMemLazyEnablePeerAccess));
-        xf.peers.region[rank] = (unsigned char*)base; xf.opened[rank] = true;
+        xf.opened[rank].open(h);      // (a mapping opened for this rank before is closed first)
+        void* const base = xf.opened[rank].h;
+        xf.peers.region[rank] = (unsigned char*)base;
         // the peer may have been created with another capacity than this rank: its own header is the authority on what fits there
         MHIP_HIP(hipMemcpy(&xf.peer_cap[rank], (unsigned char*)base + offsetof(XferHeader, rows_cap), sizeof(int64_t), hipMemcpyDeviceToHost));
         xf.plan.area[rank] = (unsigned char*)base + xfer_plan_off<T>(xf.peer_cap[rank]);
@@ -2182,7 +2148,7 @@ template <class T> class Engine final : public EngineBase {
         if (!rt) { xf.routes = false; return; }
         if (!hp_set) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_plan first"};
         if (rt->n_peers < 0 || rt->n_peers >= XFER_MAX_RANKS) throw ApiError{MHIP_ERR_INVALID, "halo routes: peer count out of range"};
-        if (rt->n_peers > 0 && !xf.region) throw ApiError{MHIP_ERR_STATE, "mhip_halo_region first"};
+        if (rt->n_peers > 0 && !xf.region.p) throw ApiError{MHIP_ERR_STATE, "mhip_halo_region first"};
         std::vector<int32_t> rp, rd; rp.reserve((size_t)hp.n_send_rows); rd.reserve((size_t)hp.n_send_rows);
         int64_t recv_total = 0;
         xf.peer_rank.assign(rt->peer_rank, rt->peer_rank + rt->n_peers);
@@ -2205,13 +2171,13 @@ template <class T> class Engine final : public EngineBase {
     // into every rank's table and waits (bounded) for all of theirs.  0 = some rank's store did not become visible here within 2 s —
     // the host then keeps its own loop with torch.distributed collectives (every rank must call this at the same point).
     int halo_selftest() override {
-        if (!xf.region) throw ApiError{MHIP_ERR_STATE, "mhip_halo_region first"};
+        if (!xf.region.p) throw ApiError{MHIP_ERR_STATE, "mhip_halo_region first"};
         for (int r = 0; r < xf.world; ++r) if (!xf.peers.region[r]) throw ApiError{MHIP_ERR_STATE, "mhip_halo_open_peer for every rank first"};
         const float token[4] = {(float)(xf.rank + 1), 0.f, 0.f, 0.f};
         MHIP_HIP(hipMemcpyAsync(xf.mine3.p, token, 3 * sizeof(float), hipMemcpyHostToDevice, stream));
         ++xf.plan_seq;
         hipLaunchKernelGGL(k_plan_push, dim3(1), dim3(64), 0, stream, (const float*)xf.mine3.p, xf.peers, xf.world, xf.rank, (int)(xf.plan_seq & 1u), xf.plan_seq);
-        hipLaunchKernelGGL(k_plan_reduce, dim3(1), dim3(64), 0, stream, reinterpret_cast<const XferHeader*>(xf.region), xf.world, (int)(xf.plan_seq & 1u), xf.plan_seq, xf.red3.p, xf.h_red3, xf.err.p, xf_ticks());
+        hipLaunchKernelGGL(k_plan_reduce, dim3(1), dim3(64), 0, stream, reinterpret_cast<const XferHeader*>(xf.region.p), xf.world, (int)(xf.plan_seq & 1u), xf.plan_seq, xf.red3.p, xf.h_red3, xf.err.p, xf_ticks());
         MHIP_HIP(hipMemcpyAsync(xf.h_err, xf.err.p, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
         MHIP_HIP(hipStreamSynchronize(stream));
         const bool ok = *xf.h_err == 0 && xf.h_red3[0] == (float)xf.world;      // the MAX of the tokens is the highest rank's
@@ -2233,7 +2199,7 @@ template <class T> class Engine final : public EngineBase {
         return std::string(": waited for ") + what[k < 10 ? k : 0] + " of rank " + std::to_string(who & 0xff) + ", sequence number " + std::to_string((uint32_t)e[2]) + ", last seen " + std::to_string((uint32_t)e[3]);
     }
     void xf_check_errors() {
-        if (!xf.region) return;
+        if (!xf.region.p) return;
         MHIP_HIP(hipMemcpyAsync(xf.h_err, xf.err.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
         MHIP_HIP(hipStreamSynchronize(stream));
         if (*xf.h_err) {
@@ -2252,7 +2218,7 @@ template <class T> class Engine final : public EngineBase {
         ++xf.plan_seq;
         if (xf.world > 1) {
             hipLaunchKernelGGL(k_plan_push, dim3(1), dim3(64), 0, stream, (const float*)xf.mine3.p, xf.peers, xf.world, xf.rank, (int)(xf.plan_seq & 1u), xf.plan_seq);
-            hipLaunchKernelGGL(k_plan_reduce, dim3(1), dim3(64), 0, stream, reinterpret_cast<const XferHeader*>(xf.region), xf.world, (int)(xf.plan_seq & 1u), xf.plan_seq, xf.red3.p, xf.h_red3, xf.err.p, xf_ticks());
+            hipLaunchKernelGGL(k_plan_reduce, dim3(1), dim3(64), 0, stream, reinterpret_cast<const XferHeader*>(xf.region.p), xf.world, (int)(xf.plan_seq & 1u), xf.plan_seq, xf.red3.p, xf.h_red3, xf.err.p, xf_ticks());
         } else MHIP_HIP(hipMemcpyAsync(xf.h_red3, xf.mine3.p, 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
         MHIP_HIP(hipEventRecord(xf.ev_plan, stream));
         xf.plan_pending = true; xf.plan_step = s; xf.plan_prune_id = n_filters; xf.plan_outer_id = n_outer;
@@ -2267,7 +2233,7 @@ template <class T> class Engine final : public EngineBase {
         if (!hp_set) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_plan first"};
         const bool solo = hp.n_cm_peers == 0 && hp.n_send_rows == 0;
         if (!solo && !xf.routes) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_routes first"};
-        if (!xf.h_red3) { MHIP_HIP(hipHostMalloc((void**)&xf.h_red3, 4 * sizeof(float))); MHIP_HIP(hipEventCreateWithFlags(&xf.ev_plan, hipEventDisableTiming)); xf.mine3.reserve(4); xf.world = std::max(xf.world, 1); }
+        xf_plan_words(); xf.world = std::max(xf.world, 1);      // (a run without a region: one brick)
         *steps_done = 0; *reason = 0;
         if (n_steps <= 0) return;
         const int every = rebuild_every();
@@ -2360,7 +2326,7 @@ template <class T> class Engine final : public EngineBase {
     struct Dom {
         bool ready = false; int world = 1, me = 0; int64_t n_replans = 0, n_migrated = 0; double plan_ms = 0, search_ms = 0;      // host wall time inside the re-plans: planning (launches + the one sync) / the search behind it
         DBuf<int64_t> gid[2]; int gcur = 0;
-        DBuf<RpTab> tab; RpTab* h_tab = nullptr; T* h_lj0 = nullptr;
+        DBuf<RpTab> tab; Pinned<RpTab> h_tab; Pinned<T> h_lj0;
         DBuf<uint32_t> mask; DBuf<int32_t> blk_cnt, blk_off, err, ranks;
         DBuf<int32_t> send_idx, send_cm_pos, recv_dst; DBuf<T> send_shift;
         int64_t tables_cap = 0;
@@ -2369,13 +2335,6 @@ template <class T> class Engine final : public EngineBase {
     const bool dev_replan_env = env_int("MOLLYHIP_DEVICE_REPLAN", 1) != 0;
     bool replan_now = false;
     T uni_s0 = T(0), uni_e0 = T(0);      // σ, ϵ of the one atom type the uniform-LJ constants were made for (set_atoms)
-
-    void dom_release() {
-        dom.gid[0].release(); dom.gid[1].release(); dom.tab.release(); dom.mask.release(); dom.blk_cnt.release(); dom.blk_off.release(); dom.err.release(); dom.ranks.release();
-        dom.send_idx.release(); dom.send_cm_pos.release(); dom.recv_dst.release(); dom.send_shift.release();
-        if (dom.h_tab) (void)hipHostFree(dom.h_tab); if (dom.h_lj0) (void)hipHostFree(dom.h_lj0);
-        dom.h_tab = nullptr; dom.h_lj0 = nullptr; dom.ready = false;
-    }
 
     // ≙ BrickGrid of molly.jl_amd/domain.py: the bricks, this rank's neighbour directions sorted by (peer rank, direction vector), the periodic shift of
     // each, the face thresholds in T — every number formed the way the host planner forms it, so that both planners select the same atoms
@@ -2432,8 +2391,7 @@ template <class T> class Engine final : public EngineBase {
         else { std::vector<int64_t> io((size_t)n_owned); for (int64_t i = 0; i < n_owned; ++i) io[i] = i; MHIP_HIP(hipMemcpy(dom.gid[0].p, io.data(), io.size() * sizeof(int64_t), hipMemcpyHostToDevice)); }
         dom.tab.reserve(1); dom.err.reserve(4); dom.ranks.reserve(XFER_MAX_RANKS);
         MHIP_HIP(hipMemsetAsync(dom.err.p, 0, 4 * sizeof(int32_t), stream));
-        if (!dom.h_tab) MHIP_HIP(hipHostMalloc((void**)&dom.h_tab, sizeof(RpTab)));
-        if (!dom.h_lj0) MHIP_HIP(hipHostMalloc((void**)&dom.h_lj0, 2 * sizeof(T)));
+        dom.h_tab.make(1); dom.h_lj0.make(2);
         std::vector<int32_t> others; for (int r = 0; r < world; ++r) if (r != me) others.push_back(r);
         if (!others.empty()) MHIP_HIP(hipMemcpyAsync(dom.ranks.p, others.data(), others.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
         MHIP_HIP(hipStreamSynchronize(stream));
@@ -2454,7 +2412,7 @@ template <class T> class Engine final : public EngineBase {
     bool dev_replan_ok() const {
         if (!dom.ready || !dev_replan_env || !hp_set || caller_indexed_topology()) return false;
         if (dom.world == 1) return n_ghost == 0;
-        if (!xf.region || !xf.routes || xf.n_peers != dom.world - 1 || xf.world != dom.world || hp.cm_rows != dom_g.cm_rows) return false;
+        if (!xf.region.p || !xf.routes || xf.n_peers != dom.world - 1 || xf.world != dom.world || hp.cm_rows != dom_g.cm_rows) return false;
         for (int r = 0; r < dom.world; ++r) if (!xf.peers.region[r] || !xf.plan.area[r]) return false;
         return true;
     }
@@ -2487,7 +2445,7 @@ template <class T> class Engine final : public EngineBase {
         }
         dom.mask.reserve(cap); dom.blk_cnt.reserve((size_t)RP_MAX_DIRS * nb); dom.blk_off.reserve((size_t)RP_MAX_DIRS * nb);
         const uint32_t seq = ++xf.rp_seq;
-        const XferHeader* mine = reinterpret_cast<const XferHeader*>(xf.region);
+        const XferHeader* mine = reinterpret_cast<const XferHeader*>(xf.region.p);
         const unsigned long long ticks = xf_ticks();
         const int n_old = (int)n_owned;
         MHIP_HIP(hipMemsetAsync(dom.tab.p, 0, sizeof(RpTab), stream));
@@ -2689,7 +2647,7 @@ template <class T> class Engine final : public EngineBase {
     }
 
     // ---- SHAKE_RATTLE (constraints.h): clusters built on the host, one lane per cluster between consecutive force passes -----------------
-    ClusterSet con; DBuf<int32_t> con_atoms; DBuf<double> con_d; DBuf<unsigned long long> con_stat; unsigned long long* h_con = nullptr;
+    ClusterSet con; DBuf<int32_t> con_atoms; DBuf<double> con_d; DBuf<unsigned long long> con_stat; Pinned<unsigned long long> h_con;
     bool con_on = false; double con_tol = 1e-8; int32_t con_iters = 25;
     int64_t con_last_max = 0, con_fails = 0;
     bool constrained() const override { return con_on; }
@@ -2731,7 +2689,7 @@ template <class T> class Engine final : public EngineBase {
             if (!cs.vs_rec.empty()) MHIP_HIP(hipMemcpy(vs_hrec.p, cs.vs_rec.data(), cs.vs_rec.size() * sizeof(int32_t), hipMemcpyHostToDevice));
             if (!cs.vs_w.empty()) MHIP_HIP(hipMemcpy(vs_hw.p, cs.vs_w.data(), cs.vs_w.size() * sizeof(double), hipMemcpyHostToDevice));
         } else { vs_item.release(); vs_hrec.release(); vs_hw.release(); }
-        if (!h_con) MHIP_HIP(hipHostMalloc((void**)&h_con, 2 * sizeof(unsigned long long)));
+        h_con.make(2);
         h_con[0] = h_con[1] = 0;
         con = std::move(cs);
     }
@@ -2978,7 +2936,6 @@ template <class T> class Engine final : public EngineBase {
             MHIP_HIP(hipMemcpyAsync(oj, dj.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
             MHIP_HIP(hipMemcpyAsync(osp, ds.p, n * sizeof(uint8_t), hipMemcpyDeviceToHost, stream));
             MHIP_HIP(hipStreamSynchronize(stream));
-            di.release(); dj.release(); ds.release();
         }
         return (int64_t)n;
     }
@@ -3157,12 +3114,14 @@ int32_t mhip_andersen(mhip_ctx* ctx, double kT, double prob, uint64_t key, uint6
 int32_t mhip_set_andersen(mhip_ctx* ctx, double kT, double prob, uint64_t seed) { NEED_CTX(); return guard(ctx, [&] { ctx->e->set_andersen(kT, prob, seed); }); }
 int32_t mhip_philox4x32_10(const uint32_t* ctr4, const uint32_t* key2, uint32_t* out4) {
     if (!ctr4 || !key2 || !out4) return MHIP_ERR_INVALID;
-    uint32_t *in = nullptr, *out = nullptr, h[6] = {ctr4[0], ctr4[1], ctr4[2], ctr4[3], key2[0], key2[1]};
-    if (hipMalloc((void**)&in, sizeof(h)) != hipSuccess || hipMalloc((void**)&out, 4 * sizeof(uint32_t)) != hipSuccess) { (void)hipFree(in); return MHIP_ERR_HIP; }
-    bool ok = hipMemcpy(in, h, sizeof(h), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) { mhip::launch_philox_probe(nullptr, in, out); ok = hipMemcpy(out4, out, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess; }
-    (void)hipFree(in); (void)hipFree(out);
-    return ok ? MHIP_OK : MHIP_ERR_HIP;
+    const uint32_t h[6] = {ctr4[0], ctr4[1], ctr4[2], ctr4[3], key2[0], key2[1]};
+    try {
+        mhip::DBuf<uint32_t> in, out;
+        in.set(h, 6); out.alloc(4);
+        mhip::launch_philox_probe(nullptr, in.p, out.p);
+        MHIP_HIP(hipMemcpy(out4, out.p, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    } catch (const mhip::HipErr&) { return MHIP_ERR_HIP; }
+    return MHIP_OK;
 }
 int32_t mhip_specific_virial(mhip_ctx* ctx, double* out9) { NEED_CTX(); return guard(ctx, [&] { if (!out9) throw mhip::ApiError{MHIP_ERR_INVALID, "null output"}; ctx->e->specific_virial(out9); }); }
 int32_t mhip_general_virial(mhip_ctx* ctx, double* out9) { NEED_CTX(); return guard(ctx, [&] { if (!out9) throw mhip::ApiError{MHIP_ERR_INVALID, "null output"}; ctx->e->general_virial(out9); }); }

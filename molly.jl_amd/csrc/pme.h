@@ -14,6 +14,7 @@
 #pragma once
 #include <vector>
 
+#include "owners.h"
 #include "physics.h"
 #include "pme_fft.h"
 
@@ -608,21 +609,13 @@ __global__ void __launch_bounds__(PME_THREADS) k_pme_conv(DftArgs<T> A) {
     }
 }
 
-template <class U> struct PBuf {
-    U* p = nullptr; size_t n = 0;
-    void set(const std::vector<U>& h) { release(); n = h.size(); if (n) { MHIP_HIP(hipMalloc((void**)&p, n * sizeof(U))); MHIP_HIP(hipMemcpy(p, h.data(), n * sizeof(U), hipMemcpyHostToDevice)); } }
-    void alloc(size_t m) { release(); n = m; if (n) MHIP_HIP(hipMalloc((void**)&p, n * sizeof(U))); }
-    void update(const std::vector<U>& h) { if (h.size() != n) { set(h); return; } if (n) MHIP_HIP(hipMemcpy(p, h.data(), n * sizeof(U), hipMemcpyHostToDevice)); }      // same length: the allocation stays
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-
 template <class T> struct Pme {
     using T4 = typename Vec<T>::T4;
     using T2 = typename Vec<T>::T2;
     int order = 0;
     PmeP<T> P;
-    PBuf<T2> grid, tw[3];
-    PBuf<T> mh[3], bsm[3], rgrid, phi; // rgrid: real charge mesh; phi: real potential mesh
+    DBuf<T2> grid, tw[3];
+    DBuf<T> mh[3], bsm[3], rgrid, phi; // rgrid: real charge mesh; phi: real potential mesh
     int nzh = 0;                       // half-spectrum length along z
     bool fft = false; FftPlan3d plan;  // transforms by the FFT library: an axis longer than 512 points (MOLLYHIP_PME_FFT=1: always, =0: never)
     double self_factor = 0, charge_factor = 0;   // E_self = −f/ϵr·α/√π·Σq²  and  E_charge = −f/ϵr·π/(2Vα²)·(Σq)²   (:917-927)

@@ -8,8 +8,12 @@ namespace mhip {
 
 struct FftPlan3d {
     void* r2c = nullptr; void* c2r = nullptr; bool dbl = false;
+    FftPlan3d() = default;
+    FftPlan3d(const FftPlan3d&) = delete;
+    FftPlan3d& operator=(const FftPlan3d&) = delete;
+    ~FftPlan3d() { destroy(); }
     void create(int nx, int ny, int nz, bool double_precision);
-    void destroy();
+    void destroy();      // back to no plans (never throws)
     void forward(hipStream_t s, void* real_in, void* complex_out);      // real [nx][ny][nz] → complex [nx][ny][nz/2 + 1]
     void backward(hipStream_t s, void* complex_in, void* real_out);     // Hermitian half → real (the complex input may be overwritten)
 };

@@ -140,12 +140,12 @@ inline void launch_pme_bonded_fused(hipStream_t s, Pme<T>& pme, Bonded<T>& bonde
     auto gather = [&](auto order_tag) {
         constexpr int ORDER = decltype(order_tag)::value;
         hipLaunchKernelGGL((k_gather_collect<T, ORDER>), dim3(n_gather + n_collect), dim3(256), 0, s, n_owned, pos, (const T*)pme.phi.p, frc, pme.P, n_gather, orig,
-                           (const int32_t*)bonded.role_start.p, (const int32_t*)bonded.role_slot.p, (const typename Vec<T>::T4*)bonded.slots, side, bonded.fold_parts, bonded.fold_n, bonded.fold_stride);
+                           (const int32_t*)bonded.role_start.p, (const int32_t*)bonded.role_slot.p, (const typename Vec<T>::T4*)bonded.slots.p, side, bonded.fold_parts, bonded.fold_n, bonded.fold_stride);
     };
     if (vv) {
         GcvArgs<T> V = *vv;
         V.n_atoms = n_owned; V.pos = const_cast<typename Vec<T>::T4*>(pos); V.frc = frc; V.phi = (const T*)pme.phi.p; V.P = pme.P;
-        V.orig = orig; V.role_start = (const int32_t*)bonded.role_start.p; V.role_slot = (const int32_t*)bonded.role_slot.p; V.slots = (const typename Vec<T>::T4*)bonded.slots;
+        V.orig = orig; V.role_start = (const int32_t*)bonded.role_start.p; V.role_slot = (const int32_t*)bonded.role_slot.p; V.slots = (const typename Vec<T>::T4*)bonded.slots.p;
         V.parts = bonded.fold_parts; V.n_parts = bonded.fold_n; V.part_stride = bonded.fold_stride;
         if (lang) {
             if (pme.order == 4) hipLaunchKernelGGL((k_gather_collect_vv<T, 4, true>), dim3(n_gather), dim3(256), 0, s, V);

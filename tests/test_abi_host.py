@@ -145,3 +145,27 @@ def test_header_is_plain_c_and_a_c_client_links(tmp_path):
     lib_dir = os.path.join(root, "molly.jl_amd")
     subprocess.run(["gcc", "-std=c99", "-Wno-pedantic", "-I", os.path.join(root, "include"), str(src), "-o", str(exe), "-L", lib_dir, "-l:libmollyhip.so",
                     f"-Wl,-rpath,{lib_dir}", "-Wl,--allow-shlib-undefined"], check=True)
+
+
+def test_hip_resources_are_made_and_freed_in_the_owner_header_only():
+    """Resource lifetime is a property of the types of csrc/owners.h: no other source of the library calls the runtime's allocation, event,
+    stream or IPC-mapping create / free entry points (comments included), and hipFFT plans are made and destroyed in pme_fft.hip alone.
+    A buffer added anywhere else therefore cannot need a line in a destructor."""
+    csrc = os.path.join(ROOT, "molly.jl_amd", "csrc")
+    owned = ["hipMalloc(", "hipExtMallocWithFlags(", "hipFree(", "hipHostMalloc(", "hipHostFree(", "hipEventCreate", "hipEventDestroy(",
+             "hipStreamCreate", "hipStreamDestroy(", "hipIpcOpenMemHandle(", "hipIpcCloseMemHandle("]
+    sources = sorted(f for f in os.listdir(csrc) if f.endswith((".h", ".hip", ".cpp", ".hpp")))
+    assert "owners.h" in sources and "engine.hip" in sources and len(sources) >= 25
+    text = {f: open(os.path.join(csrc, f)).read() for f in sources}
+    for call in owned:
+        assert call.rstrip("(") in text["owners.h"], f"{call} is not in owners.h: the list of this test is out of date"
+        users = [f for f in sources if f != "owners.h" and call in text[f]]
+        assert not users, f"{call} outside owners.h: {users}"
+    for call in ("hipfftPlan", "hipfftDestroy"):
+        assert call in text["pme_fft.hip"]
+        users = [f for f in sources if f != "pme_fft.hip" and call in text[f]]
+        assert not users, f"{call} outside pme_fft.hip: {users}"
+    # the owners cannot be copied (a copy would be a double free), and the engine's destructor keeps no release list
+    assert text["owners.h"].count("= delete") >= 6 and "is_copy_constructible" in text["owners.h"]
+    dtor = text["engine.hip"][text["engine.hip"].index("~Engine()"):]
+    assert "release" not in dtor[:dtor.index("\n    }\n")]
