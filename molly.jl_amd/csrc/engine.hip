@@ -21,6 +21,7 @@
 #include "step_fused.h"
 #include "hilbert.h"
 #include "kernels.h"
+#include "list_policy.h"
 #include "replan.h"
 #include "halo_step.h"
 #include "forces_launch.h"
@@ -204,26 +205,27 @@ template <class T> class Engine final : public EngineBase {
     }
     DBuf<int32_t> blk_ghost, blk_ghost_in; bool ghost_flags_ok = false, ghost_flags_in_ok = false;
     bool interior_done = false;      // halo_interior ran the blocks without ghosts: the next step_forces (halo_end, a separate call) runs the rest
-    int64_t last_prune_step = 0;
     int64_t pass_step = 0;       // the MD step whose coordinates the pair pass being launched sees (recorded as the step of a prune)
     DBuf<T4> pos_snap_in;        // coordinates at the last prune (validity of the inner list: 2·displacement <= skin)
-    double skin = 0; int64_t n_disp_checks = 0;
+    // when a list may live on, is pruned again, is searched again: the rule and the numbers it goes by (list_policy.h)
+    ListPolicy lp = [] { ListPolicy p; p.inner_skin_fixed = env_int("MOLLYHIP_INNER_SKIN_FIXED", 0) != 0; return p; }();
+    static double inner_skin_floor() { return std::max(1, env_int("MOLLYHIP_INNER_SKIN_PM", 100)) * 1e-3; }   // (read at each use: a context may be made under another value)
     // The inner list of the dual scheme only has to hold every pair inside the CUTOFFS (mhip_export_neighbors filters the outer list to
     // r_list itself): it is pruned to rc_max + skin_in, skin_in <= skin.  A smaller radius means fewer entries per force pass (∝ r³) and
     // more frequent prunes; MOLLYHIP_INNER_SKIN_PM (picometres, default 100) sets it, the ghosted path keeps skin_in = skin.
-    double skin_in = 0, rc_max_ = 0; T r_prune2 = 0;
+    T r_prune2 = 0;
+    void set_prune_radius() { const T rp = T(lp.rc_max + lp.skin_in); r_prune2 = (lp.skin_in < lp.skin) ? rp * rp : r_in2; }
     // ghosted sub-domain whose ghost shell reaches r_list + ghost_margin: the ghost PLAN then lives as long as an outer list
     // (until some atom moved ghost_margin/2), so the dual list works here too and the host re-plans only when mhip_plan_disp2_dev says so
     double ghost_margin = 0;
     int tri_mode = 0; double tri_bv[9] = {};   // TriclinicBoundary: 0 off, 1 approx_images, 2 exact images; basis vectors row-major
     bool tri_grid = false;                     // … with a cell grid in height-scaled fractional coordinates (else: one cell, every block sees every atom)
     long long grid_key = -1;
-    double skin_in_adapted = 0;
     bool engine_sched = false;   // … unless it hands the reduced displacements to mhip_plan_decide: then the engine's own criteria (inner skin, drift bound) decide
     bool host_prune = false;     // ghost plans: the HOST decides, collectively over the ranks, when the inner list is re-pruned (mhip_request_prune)
     // single list, same idea: a rebuild step whose displacement check shows the list still covers every cutoff sphere is skipped
-    bool lazy_single = false; int64_t n_skipped = 0;
-    bool dual = false, dual_disabled = false, margin_zero = false, want_margin_zero = false; int margin_halvings = 0; int early_outer = 0; double outer_margin = 0; int64_t last_outer_step = 0, n_outer = 0, n_filters = 0; T r_in = 0, r_in2 = 0;
+    bool lazy_single = false;
+    bool dual = false, dual_disabled = false, margin_zero = false; int margin_halvings = 0; int64_t n_outer = 0, n_filters = 0; T r_in = 0, r_in2 = 0;
     DBuf<int32_t> flags; Pinned<int32_t> h_flags;
     int64_t total_rows = 0, outer_rows = 0;      // rows (of four entries per lane, per wave) of the list the plain passes walk | of the outer list as searched
     // reductions
@@ -330,11 +332,11 @@ template <class T> class Engine final : public EngineBase {
         r_in2 = G.no_list ? std::numeric_limits<T>::infinity() : r_in * r_in;                 // dist_cutoff^2, neighbors.jl:400
         // dual pair list: search with r_list + margin (MOLLYHIP_OUTER_MARGIN_PM in picometres, 0 disables), prune to the inner radius when displacement
         // says so, search again when the margin is used up
-        outer_margin = (G.no_list || dual_disabled) ? 0.0 : std::ldexp(env_int("MOLLYHIP_OUTER_MARGIN_PM", 200) * 1e-3, -margin_halvings);
+        lp.outer_margin = (G.no_list || dual_disabled) ? 0.0 : std::ldexp(env_int("MOLLYHIP_OUTER_MARGIN_PM", 200) * 1e-3, -margin_halvings);
         // margin 0 keeps the two-list machinery without the wider search: the list is built with r_list and pruned once, right away —
         // which compacts the tile to the atoms the rows refer to (a tile that needed two LDS segments in fp64 then fits in one)
-        if (margin_zero && n_ghost == 0) outer_margin = 0;
-        if (n_ghost > 0) outer_margin = std::min(outer_margin, ghost_margin);   // the shell handed over must cover the outer radius
+        if (margin_zero && n_ghost == 0) lp.outer_margin = 0;
+        if (n_ghost > 0) lp.outer_margin = std::min(lp.outer_margin, ghost_margin);   // the shell handed over must cover the outer radius
         // extent of the cell grid per axis: the box side, or — TriclinicBoundary — the perpendicular height of the cell along that
         // axis (the grid lives in u = s·h, common.h): h = V / |b × c|, V / |c × a|, V / |a × b| for the basis a ∥ x, b in the xy plane
         double ext[3] = {cfg.box[0], cfg.box[1], cfg.box[2]};
@@ -344,7 +346,7 @@ template <class T> class Engine final : public EngineBase {
             auto cross_norm = [](const double* u, const double* v) { const double x = u[1] * v[2] - u[2] * v[1], y = u[2] * v[0] - u[0] * v[2], z = u[0] * v[1] - u[1] * v[0]; return std::sqrt(x * x + y * y + z * z); };
             ext[0] = V / cross_norm(b, c); ext[1] = V / cross_norm(c, a); ext[2] = V / cross_norm(a, b);
         }
-        for (int d = 0; d < 3; ++d) if (cfg.periodic[d] && cfg.r_list + outer_margin > 0.5 * ext[d]) outer_margin = 0;   // keep r_outer <= L/2 (triclinic: half the cell height)
+        for (int d = 0; d < 3; ++d) if (cfg.periodic[d] && cfg.r_list + lp.outer_margin > 0.5 * ext[d]) lp.outer_margin = 0;   // keep r_outer <= L/2 (triclinic: half the cell height)
         // walking the outer list is only equivalent to walking the reference's list if every interaction vanishes beyond a
         // cutoff <= r_list; a NoCutoff interaction summed over a neighbour list depends on list membership itself
         const mhip_interactions& ip = cfg.inter;
@@ -354,11 +356,10 @@ template <class T> class Engine final : public EngineBase {
             double rc_max = 0;
             if (ip.lj_enabled) rc_max = std::max(rc_max, ip.lj_rc);
             if (ip.coul_kind != MHIP_COUL_NONE) rc_max = std::max(rc_max, ip.coul_rc);
-            skin = G.no_list ? 0.0 : cfg.r_list - rc_max;
-            rc_max_ = rc_max;
-            skin_in = ((n_ghost > 0 || host_prune) && !engine_sched) ? skin : std::min(skin, std::max(skin_in_adapted, inner_skin_floor()));   // (a skin the run has grown stays grown)
-            const T rp = T(rc_max + skin_in);
-            r_prune2 = (skin_in < skin) ? rp * rp : r_in2;
+            lp.skin = G.no_list ? 0.0 : cfg.r_list - rc_max;
+            lp.rc_max = rc_max;
+            lp.start_inner_skin(!((n_ghost > 0 || host_prune) && !engine_sched), inner_skin_floor());
+            set_prune_radius();
         }
         const int S = 2;      // cells of >= r_search / 2 per side of the stencil
         // A TriclinicBoundary keeps the dual list and the displacement-skipped rebuilds when the box still gets a real cell grid with the
@@ -366,12 +367,12 @@ template <class T> class Engine final : public EngineBase {
         // Cartesian coordinates, kernels.h); a box too small for a grid keeps the one-cell form: plain fixed-cadence lists, exact images.
         bool tri_lists_ok = !tri_mode;
         if (tri_mode && !G.no_list)
-            for (int d = 0; d < 3; ++d) tri_lists_ok = tri_lists_ok || (int)std::floor(ext[d] / ((cfg.r_list + outer_margin) / S)) > 2 * S + 1;
-        if (!tri_lists_ok) outer_margin = 0;
-        dual = (outer_margin > 0 || (margin_zero && n_ghost == 0 && !G.no_list && !dual_disabled)) && lj_cut_ok && coul_cut_ok && skin > 0 && tri_lists_ok;   // ghosted: only with a ghost margin (else re-planned every rebuild)
-        lazy_single = !dual && !G.no_list && lj_cut_ok && coul_cut_ok && skin > 0 && n_ghost == 0 && tri_lists_ok;
-        if (debug_on) std::fprintf(stderr, "[mhip] grid: dual %d margin %.3f skin %.3f lj_ok %d coul_ok %d ghosts %lld\n", (int)dual, outer_margin, skin, (int)lj_cut_ok, (int)coul_cut_ok, (long long)n_ghost);
-        const double r_search = G.no_list ? 0.0 : cfg.r_list + (dual ? outer_margin : 0.0);
+            for (int d = 0; d < 3; ++d) tri_lists_ok = tri_lists_ok || (int)std::floor(ext[d] / ((cfg.r_list + lp.outer_margin) / S)) > 2 * S + 1;
+        if (!tri_lists_ok) lp.outer_margin = 0;
+        dual = (lp.outer_margin > 0 || (margin_zero && n_ghost == 0 && !G.no_list && !dual_disabled)) && lj_cut_ok && coul_cut_ok && lp.skin > 0 && tri_lists_ok;   // ghosted: only with a ghost margin (else re-planned every rebuild)
+        lazy_single = !dual && !G.no_list && lj_cut_ok && coul_cut_ok && lp.skin > 0 && n_ghost == 0 && tri_lists_ok;
+        if (debug_on) std::fprintf(stderr, "[mhip] grid: dual %d margin %.3f skin %.3f lj_ok %d coul_ok %d ghosts %lld\n", (int)dual, lp.outer_margin, lp.skin, (int)lj_cut_ok, (int)coul_cut_ok, (long long)n_ghost);
+        const double r_search = G.no_list ? 0.0 : cfg.r_list + (dual ? lp.outer_margin : 0.0);
         G.r_list = G.no_list ? std::numeric_limits<T>::infinity() : T(r_search);
         G.r_list2 = G.no_list ? std::numeric_limits<T>::infinity() : (dual ? G.r_list * G.r_list : r_in2);
         tri_grid = false;
@@ -444,7 +445,6 @@ template <class T> class Engine final : public EngineBase {
     void reblock() { choose_blocking(); stale = true; }
     void regrid() { setup_grid(); reblock(); }
     int rebuild_every() const { return cfg.rebuild_every > 0 ? cfg.rebuild_every : 10; }
-    static double inner_skin_floor() { return std::max(1, env_int("MOLLYHIP_INNER_SKIN_PM", 100)) * 1e-3; }   // (read at each use: a context may be made under another value)
 
     // ≙ set_cuda_launch_config! / reset_cuda_launch_config! (src/cuda_config.jl:17-47): the workgroup shape of the search and pair
     // kernels, block_atoms i-atoms × j_split waves per atom's list; (0, 0) returns to the automatic choice.  Lists are rebuilt.
@@ -481,7 +481,7 @@ template <class T> class Engine final : public EngineBase {
             float us = -1.f;
             try {
                 user_bi = c[0]; user_js = c[1];
-                reblock(); cur_dt = 0;
+                reblock(); lp.cur_dt = 0;
                 ensure_built(step); pass_step = step;
                 launch_pair_kernel(false);                     // with a dual list: the pruning pass
                 if (prune_disp_exceeded) { after_forces(step); launch_pair_kernel(false); }
@@ -511,7 +511,7 @@ template <class T> class Engine final : public EngineBase {
         if (G.no_list) { T_cap = (int)n_tot + 8; R_cap = cdiv(n_tot, 4) + 2; C_cap = 8; }
         else if (tri_mode && !tri_grid) { T_cap = (int)n_tot + 8; R_cap = (int)std::min<double>(1.5 * rho * 4.0 / 3.0 * M_PI * std::pow(cfg.r_list, 3) / 4 / JS + 8, n_tot / 4.0 + 2); C_cap = 8; }
         else {
-            double r = (cfg.r_list + (dual ? outer_margin : 0.0)) * 1.001, a = std::cbrt(BI / rho);
+            double r = (cfg.r_list + (dual ? lp.outer_margin : 0.0)) * 1.001, a = std::cbrt(BI / rho);
             double v_tile = a * a * a + 6 * a * a * r + 3 * M_PI * a * r * r + 4.0 / 3.0 * M_PI * r * r * r;
             if (tri_grid) v_tile = (a + 2 * r) * (a + 2 * r) * (a + 2 * r) * 1.3;   // per-axis (Chebyshev) pruning in a skewed frame: a box, not a rounded one
             T_cap = (int)std::min<double>(1.4 * rho * v_tile + 64, (double)n_tot + 8);
@@ -556,7 +556,7 @@ template <class T> class Engine final : public EngineBase {
             // (a sub-domain of a multi-GPU run never shrinks its margin on its own: the ranks decide prunes and re-plans from the same
             // numbers, mhip_plan_decide — without the dual list mhip_plan_state_dev reports +inf and every rank re-plans at every rebuild step)
             if (n_ghost > 0 || ghost_margin > 0 || host_prune) dual_disabled = true;
-            else if (outer_margin > 0.06) ++margin_halvings; else if (!margin_zero) margin_zero = true; else dual_disabled = true;
+            else if (lp.outer_margin > 0.06) ++margin_halvings; else if (!margin_zero) margin_zero = true; else dual_disabled = true;
             if (debug_on) std::fprintf(stderr, "[mhip] dual list %s (capacity): %s\n", dual_disabled ? "off" : (margin_zero ? "without outer margin" : "margin halved"), e.msg.c_str());
             regrid();
             rebuild(step_n);
@@ -564,7 +564,7 @@ template <class T> class Engine final : public EngineBase {
     }
 
     void rebuild_impl(int64_t step_n) {
-        next_check_step = -1;
+        lp.next_check_step = -1;
         const int sub_bits = (ilog2(2 * G.ncell + 1) + 1 + 6 <= 32) ? 6 : 0;      // atoms of a cell ordered by a 6-bit Morton position inside it
         if (!params_set || !state_set) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before forces"};
         auto t0 = std::chrono::steady_clock::now();
@@ -656,20 +656,21 @@ template <class T> class Engine final : public EngineBase {
         carve_force_lds(max_tile);
         red_part.reserve(std::max<size_t>(7 * (size_t)n_blocks, 4 * (size_t)cdiv(n_owned, 256)) + 8);
         bonded.on_reorder();
-        ++n_outer; last_outer_step = step_n;
+        ++n_outer; lp.last_outer_step = step_n;
         if (dual) {   // remember where everybody was; the next force pass prunes the outer list into the inner one
             pos_snap.reserve(cap);
             MHIP_HIP(hipMemcpyAsync(pos_snap.p, pos[cur].p, (size_t)n_tot * sizeof(T4), hipMemcpyDeviceToDevice, stream));
             inner_valid = false; inner_is_outer = false; prune_disp_exceeded = false; ghost_flags_in_ok = false;
-            if (cur_dt > 0 && skin_in < skin && !host_prune) {   // inside a run: how fast is the fastest atom? (sizes the inner skin before the first prune)
+            if (lp.cur_dt > 0 && lp.skin_in < lp.skin && !host_prune) {   // inside a run: how fast is the fastest atom? (sizes the inner skin before the first prune)
                 (void)max_disp2_since(pos_snap);
-                adapt_inner_skin(drift_ahead(0.0, 1, rebuild_every()));
+                const double drift = lp.drift_ahead(0.0, 1, rebuild_every());
+                if (lp.grow_inner_skin(drift, n_ghost > 0)) inner_skin_grown(drift);
             }
         }
         if (lazy_single) {
             pos_snap_in.reserve(cap);
             MHIP_HIP(hipMemcpyAsync(pos_snap_in.p, pos[cur].p, (size_t)n_tot * sizeof(T4), hipMemcpyDeviceToDevice, stream));
-            last_prune_step = step_n;
+            lp.last_prune_step = step_n;
         }
         stale = false; coords_moved = false; export_needs_search = false; ghost_flags_ok = false; ghost_flags_in_ok = false; last_build_step = step_n; ++n_rebuilds;
         frc_run_total = false;   // the sort moved the atoms
@@ -720,7 +721,6 @@ template <class T> class Engine final : public EngineBase {
     }
 
     // max |x − x_snap|² over all local atoms, and the largest speed among the owned atoms (one small kernel + one host sync)
-    double last_vmax = 0, prev_vmax = 0;
     float max_disp2_since(const DBuf<T4>& snap) {
         tr("k_max_disp");
         MHIP_HIP(hipMemsetAsync(flags.p + FLAG_MAX_DISP2, 0, 2 * sizeof(int32_t), stream));
@@ -729,35 +729,14 @@ template <class T> class Engine final : public EngineBase {
         MHIP_HIP(hipMemcpyAsync(h_flags, flags.p, N_FLAGS * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
         MHIP_HIP(hipStreamSynchronize(stream));
         float d2, v2; std::memcpy(&d2, &h_flags[FLAG_MAX_DISP2], sizeof(float)); std::memcpy(&v2, &h_flags[FLAG_MAX_V2], sizeof(float));
-        prev_vmax = last_vmax; last_vmax = std::sqrt((double)v2);
-        ++n_disp_checks;
+        lp.measured(std::sqrt((double)v2));
         return d2;
     }
-    // Upper estimate of how much further anybody gets until the next displacement check, `every` steps from now.  Inside a run the
-    // time step is known: the fastest atom's speed now, stretched by how much the top speed grew since the last check (at least 10 %),
-    // times the interval.  Driven from outside through forces(step_n) there is no time step: the displacement rate seen so far, times 1.5.
-    double cur_dt = 0;
-    // The inner list must outlive at least one check interval: if the fastest atoms cover more than a third of the inner skin between
-    // two checks, the skin grows (up to the reference's own r_list − cutoff) and the list is pruned afresh with the larger radius.
-    void adapt_inner_skin(double drift_per_interval) {
-        if (!dual || (host_prune && !engine_sched) || !(skin_in < skin) || inner_skin_fixed) return;
-        const double need = std::min(skin, 3.0 * drift_per_interval / 0.98);
-        if (need <= skin_in) return;
-        skin_in = need; skin_in_adapted = need;
-        const T rp = T(rc_max_ + skin_in);
-        r_prune2 = (skin_in < skin) ? rp * rp : r_in2;
+    // the policy grew the inner skin: the prune radius follows, and the list pruned with the old one is done with
+    void inner_skin_grown(double drift_per_interval) {
+        set_prune_radius();
         inner_valid = false;
-        // An outer list serves a second prune only while nobody moved (outer_margin + skin − skin_in)/2 since its search, and the inner
-        // list is not due before ≈ skin_in/2: with outer_margin <= 2·skin_in − skin every outer list is pruned exactly once, and its
-        // margin only makes the search dearer.
-        if (n_ghost == 0 && outer_margin > 0 && outer_margin <= 2.0 * skin_in - skin + 0.02) want_margin_zero = true;
-        if (debug_on) std::fprintf(stderr, "[mhip] inner skin raised to %.3f nm (drift per check interval %.4f nm)\n", skin_in, drift_per_interval);
-    }
-    double drift_ahead(double d_so_far, int64_t steps_so_far, int every) const {
-        const double empirical = 1.5 * d_so_far * (double)every / (double)std::max<int64_t>(steps_so_far, 1);
-        if (!(cur_dt > 0)) return empirical;
-        const double growth = prev_vmax > 0 ? std::min(std::max(last_vmax / prev_vmax, 1.1), 3.0) : 1.25;
-        return last_vmax * growth * cur_dt * every;
+        if (debug_on) std::fprintf(stderr, "[mhip] inner skin raised to %.3f nm (drift per check interval %.4f nm)\n", lp.skin_in, drift_per_interval);
     }
 
     // Validity checks without a kernel or a pipeline drain of their own (mhip_vv_run's fused loop, dual list, no ghosts).  The integrator
@@ -780,90 +759,56 @@ template <class T> class Engine final : public EngineBase {
         h_trk.make(4); ev_trk.make(hipEventDisableTiming);
         hipLaunchKernelGGL(k_track_reduce, dim3(1), dim3(256), 0, stream, n_parts, (const float*)trk_part.p, trk_out.p, h_trk);   // (straight into pinned host memory)
         MHIP_HIP(hipEventRecord(ev_trk, stream));
-        trk_issued = true; trk_step = step; trk_prev_vmax = last_vmax; trk_prune_id = n_filters; trk_outer_id = n_outer;
+        trk_issued = true; trk_step = step; trk_prev_vmax = lp.last_vmax; trk_prune_id = n_filters; trk_outer_id = n_outer;
     }
     void resolve_track(int64_t step) {
         if (!trk_issued) return;
         MHIP_HIP(hipEventSynchronize(ev_trk));
         trk_issued = false;
-        const double d = std::sqrt((double)h_trk[0]), d_outer = std::sqrt((double)h_trk[1]);
-        prev_vmax = trk_prev_vmax; last_vmax = std::sqrt((double)h_trk[2]);   // (the speed of the check before, as it was when this one was issued: a run cut into chunks decides alike)
-        ++n_disp_checks;
+        const ListPolicy::Measured m{std::sqrt((double)h_trk[0]), std::sqrt((double)h_trk[1]), trk_step - lp.last_prune_step};
+        lp.measured(std::sqrt((double)h_trk[2]), trk_prev_vmax);   // (the speed of the check before, as it was when this one was issued: a run cut into chunks decides alike)
         if (!dual || stale || !inner_valid || n_ghost > 0 || n_filters != trk_prune_id || n_outer != trk_outer_id) return;   // the lists it measured have been replaced meanwhile
-        const int every = rebuild_every();
-        const int64_t so_far = trk_step - last_prune_step;
-        const double ahead = drift_ahead(d, so_far, every);
-        if (debug_on) std::fprintf(stderr, "[mhip] step %lld: measured at %lld: d %.5f d_outer %.5f v_max %.4f\n", (long long)step, (long long)trk_step, d, d_outer, last_vmax);
-        adapt_inner_skin(ahead);
-        bool reprune = !inner_valid || 2.0 * (d + ahead) > skin_in * 0.98;
-        next_check_step = -1;
-        if (reprune && inner_valid)
-            if (const int k = steps_within(d, 0.49 * skin_in, so_far, every, true)) { next_check_step = trk_step + k; reprune = false; }
-        if (!reprune) return;
-        if (2.0 * (d_outer + last_vmax * cur_dt * 1.25 * (double)(step - trk_step)) > prune_margin() * 0.98) { rebuild(step); return; }
-        inner_valid = false;
+        if (debug_on) std::fprintf(stderr, "[mhip] step %lld: measured at %lld: d %.5f d_outer %.5f v_max %.4f\n", (long long)step, (long long)trk_step, m.d, m.d_outer, lp.last_vmax);
+        const ListPolicy::Decision r = lp.decide(m, ListPolicy::Applied::asynchronous(rebuild_every(), trk_step, step));
+        if (r.grown) inner_skin_grown(r.ahead);
+        if (r.action == ListPolicy::SEARCH) rebuild(step);
+        else if (r.action == ListPolicy::PRUNE) inner_valid = false;
     }
 
-    // Checks between the cadence steps.  A list that cannot be vouched for over a whole interval (the fastest atom could use up the
-    // remaining slack in `every` steps) may still be good for k < every steps: instead of giving it up now, look again in k steps.
-    // Light, fast atoms (hydrogens at 0.5 fs: 0.06 nm of possible drift per 10 steps against 0.1 nm of slack) otherwise cost a
-    // search at nearly every interval.  Only inside mhip_vv_run / mhip_langevin_run, which own the step loop.
-    int64_t next_check_step = -1;
-    bool check_due(int64_t step, int every) const { return step % every == 0 || (next_check_step >= 0 && step >= next_check_step); }
-    // largest k < every such that a displacement of d now stays within `limit` for k more steps (0: none worth a check of its own)
-    int steps_within(double d, double limit, int64_t steps_so_far, int every, bool caller_owns_loop = false) const {
-        if (!(in_run || caller_owns_loop)) return 0;
-        const double per_step = drift_ahead(d, steps_so_far, 1);
-        if (!(per_step > 0)) return 0;
-        const int k = (int)std::min<double>(std::floor((limit - d) / per_step), every - 1);
-        return k >= 3 ? k : 0;
-    }
-    bool in_run = false;      // inside a run that owns its step loop (steps_within reads it, deep inside refresh)
+    bool in_run = false;      // inside a run that owns its step loop (only there may a decision of refresh ask for a check between the cadence steps)
     struct InRun { bool& f; explicit InRun(bool& b) : f(b) { f = true; } ~InRun() { f = false; } };
 
     // rebuild step of the cadence (find_neighbors at step_n % n_steps == 0): a fresh search, or — with the dual list —
     // a filter pass, falling back to the search when it is due or an atom moved more than half the margin
     void refresh(int64_t step_n) {
         const int every = rebuild_every();
-        if (want_margin_zero && !margin_zero && n_ghost == 0) {
-            if (debug_on) std::fprintf(stderr, "[mhip] outer margin dropped (inner skin %.3f nm leaves it no second prune)\n", skin_in);
+        if (lp.want_margin_zero && !margin_zero && n_ghost == 0) {
+            if (debug_on) std::fprintf(stderr, "[mhip] outer margin dropped (inner skin %.3f nm leaves it no second prune)\n", lp.skin_in);
             margin_zero = true; regrid();
         }
-        if (!dual && lazy_single && !stale && step_n > last_prune_step) {
+        if (!dual && lazy_single && !stale && step_n > lp.last_prune_step) {
             // single list built with r_list at step last_prune_step: it still holds every pair within the cutoffs unless somebody moved skin/2
-            const double d = std::sqrt((double)max_disp2_since(pos_snap_in));
-            if (debug_on) std::fprintf(stderr, "[mhip] step %lld: max disp %.5f nm since the build of step %lld (skin %.3f), v_max %.4f\n", (long long)step_n, d, (long long)last_prune_step, skin, last_vmax);
-            next_check_step = -1;
-            if (2.0 * (d + drift_ahead(d, step_n - last_prune_step, every)) <= skin * 0.98) { last_build_step = step_n; ++n_skipped; return; }
-            if (const int k = steps_within(d, 0.49 * skin, step_n - last_prune_step, every)) { next_check_step = step_n + k; last_build_step = step_n; ++n_skipped; return; }
+            const ListPolicy::Measured m{std::sqrt((double)max_disp2_since(pos_snap_in)), 0.0, step_n - lp.last_prune_step};
+            if (debug_on) std::fprintf(stderr, "[mhip] step %lld: max disp %.5f nm since the build of step %lld (skin %.3f), v_max %.4f\n", (long long)step_n, m.d, (long long)lp.last_prune_step, lp.skin, lp.last_vmax);
+            if (lp.decide(m, ListPolicy::Applied::lazy_single(every, step_n, in_run)).action != ListPolicy::SEARCH) { last_build_step = step_n; return; }
         }
-        if (!dual || stale || (n_ghost == 0 && step_n < last_outer_step)) { rebuild(step_n); return; }
+        if (!dual || stale || (n_ghost == 0 && step_n < lp.last_outer_step)) { rebuild(step_n); return; }
         // The inner list (pairs within r_list when it was pruned) provably contains every pair within the cutoffs as long as no atom
         // moved more than skin/2 since then — the condition the reference's fixed cadence only assumes.  Check it; re-prune (inside
         // the next force pass) only when it is about to fail.  mhip_export_neighbors always returns the exact list of NOW.
         if (host_prune && inner_valid) { last_build_step = step_n; ++n_rebuilds; return; }   // the host calls mhip_request_prune
-        bool reprune = !inner_valid;
-        if (!reprune && trk_issued && trk_step == step_n && async_ok()) {   // measured by the integrator launch that made these coordinates; decided one step later
+        if (inner_valid && trk_issued && trk_step == step_n && async_ok()) {   // measured by the integrator launch that made these coordinates; decided one step later
             last_build_step = step_n; ++n_rebuilds;
             return;
         }
-        if (!reprune) {
-            const float d2 = max_disp2_since(pos_snap_in);
-            // headroom for the drift until the next check: the displacement so far, extrapolated one more interval
-            const double d = std::sqrt((double)d2), ahead = drift_ahead(d, step_n - last_prune_step, every);
-            adapt_inner_skin(ahead);
-            reprune = !inner_valid || 2.0 * (d + ahead) > skin_in * 0.98;
-            next_check_step = -1;
-            if (reprune && inner_valid && n_ghost == 0)
-                if (const int k = steps_within(d, 0.49 * skin_in, step_n - last_prune_step, every)) { next_check_step = step_n + k; reprune = false; }
-        }
-        if (reprune && n_ghost == 0 && !stale) {
-            // a prune is only as good as the outer list behind it (nobody moved more than half the margin since the outer search):
-            // if that is already used up, search again now instead of running a prune pass that would have to be thrown away
-            const double d_outer = std::sqrt((double)max_disp2_since(pos_snap));
-            if (2.0 * d_outer > prune_margin() * 0.98) { rebuild(step_n); return; }
-        }
-        if (reprune) inner_valid = false;         // the next force pass re-prunes the outer list at the then-current coordinates
+        // the displacement since the prune now; the one since the outer search only if the decision comes to a prune (a ghosted
+        // sub-domain's outer list is its ghost plan's: the host vouches for it, mhip_plan_disp2_dev)
+        const ListPolicy::Measured m{inner_valid ? std::sqrt((double)max_disp2_since(pos_snap_in)) : (double)INFINITY, 0.0, step_n - lp.last_prune_step};
+        const ListPolicy::Decision r = lp.decide(m, ListPolicy::Applied::synchronous(every, step_n, in_run, n_ghost > 0),
+                                                 [&] { return n_ghost > 0 ? 0.0 : std::sqrt((double)max_disp2_since(pos_snap)); });
+        if (r.grown) inner_skin_grown(r.ahead);
+        if (r.action == ListPolicy::SEARCH) { rebuild(step_n); return; }
+        if (r.action == ListPolicy::PRUNE) inner_valid = false;         // the next force pass re-prunes the outer list at the then-current coordinates
         last_build_step = step_n; ++n_rebuilds;
     }
 
@@ -872,11 +817,7 @@ template <class T> class Engine final : public EngineBase {
         if (!prune_disp_exceeded) return;
         prune_disp_exceeded = false;
         if (n_ghost > 0) throw ApiError{MHIP_ERR_STATE, "an atom moved more than half the ghost margin since the ghost plan: re-plan earlier (mhip_plan_disp2_dev)"};
-        const int every = rebuild_every();
-        // If that keeps happening before the outer list has paid for itself (fast light atoms, small time step), the dual list
-        // is a loss: fall back to a fresh search at every rebuild step.
-        if (step_n - last_outer_step <= 2 * (int64_t)every) { if (++early_outer >= 3) { if (debug_on) std::fprintf(stderr, "[mhip] dual list off (outer list outrun 3x)\n"); dual_disabled = true; regrid(); } }
-        else early_outer = 0;
+        if (lp.outer_outrun(step_n, rebuild_every())) { if (debug_on) std::fprintf(stderr, "[mhip] dual list off (outer list outrun 3x)\n"); dual_disabled = true; regrid(); }
         rebuild(step_n);
     }
 
@@ -888,7 +829,7 @@ template <class T> class Engine final : public EngineBase {
     void start_lists(int64_t first_step) {
         lists_after_set_state();
         if (stale || !(dual || lazy_single)) { vel_check_due = false; rebuild(first_step); return; }
-        if ((check_due(first_step, rebuild_every()) && first_step != last_build_step) || vel_check_due) { vel_check_due = false; refresh(first_step); }
+        if ((lp.check_due(first_step, rebuild_every()) && first_step != last_build_step) || vel_check_due) { vel_check_due = false; refresh(first_step); }
     }
 
     void ensure_built(int64_t step_n) {
@@ -896,7 +837,7 @@ template <class T> class Engine final : public EngineBase {
         lists_after_set_state();
         vel_check_due = false;   // (driven from outside there is no time step: the displacement checks of set_state are all there is)
         if (stale) rebuild(step_n);
-        else if (check_due(step_n, rebuild_every()) && step_n != last_build_step) refresh(step_n);
+        else if (lp.check_due(step_n, rebuild_every()) && step_n != last_build_step) refresh(step_n);
     }
 
     // What a pruning pass leaves for the host — the pruned list's largest tile and row total, the largest displacement since the outer search — read WITHOUT draining
@@ -913,8 +854,8 @@ template <class T> class Engine final : public EngineBase {
         if (n_filters != prune_pending_id || stale || !inner_valid) return;      // the list it described has been replaced meanwhile
         float d2; std::memcpy(&d2, &h_prune[FLAG_MAX_DISP2], sizeof(float));
         total_rows = h_prune[FLAG_TOTAL_ROWS]; max_tile_in = h_prune[FLAG_MAX_TILE];
-        if (debug_on) std::fprintf(stderr, "[mhip] prune (read late): max disp %.5f nm (margin %.3f) rows %lld tile %d\n", std::sqrt((double)d2), prune_margin(), (long long)total_rows, max_tile_in);
-        if (2.0 * std::sqrt((double)d2) > prune_margin() * 0.98)
+        if (debug_on) std::fprintf(stderr, "[mhip] prune (read late): max disp %.5f nm (margin %.3f) rows %lld tile %d\n", std::sqrt((double)d2), lp.prune_margin(), (long long)total_rows, max_tile_in);
+        if (!lp.prune_stands(std::sqrt((double)d2)))
             throw ApiError{MHIP_ERR_STATE, "an atom moved more than half the ghost margin since the ghost plan: re-plan earlier (mhip_plan_disp2_dev)"};
     }
 
@@ -977,8 +918,8 @@ template <class T> class Engine final : public EngineBase {
         // dual pair list: a force pass whose inner list is stale walks the OUTER list (always a valid superset — the cutoff is
         // applied per pair) and, if it is a plain force call, prunes it into the inner list on the way
         if constexpr (std::is_same<T, float>::value) {
-            if (dual && !inner_valid && !energy && allow_gs && part == 0 && !req.frc && adopt_env && gs_groups() > 0 && cnt_outer_valid && margin_zero && !(skin_in < skin)
-                && last_outer_step == pass_step && n_ghost == 0 && !host_prune) adopt_outer_list();
+            if (dual && !inner_valid && !energy && allow_gs && part == 0 && !req.frc && adopt_env && gs_groups() > 0 && cnt_outer_valid && margin_zero && !(lp.skin_in < lp.skin)
+                && lp.last_outer_step == pass_step && n_ghost == 0 && !host_prune) adopt_outer_list();
         }
         const bool use_inner = dual && inner_valid;
         const bool prune = dual && !inner_valid && !energy;
@@ -1051,7 +992,7 @@ template <class T> class Engine final : public EngineBase {
             // the snapshot the next displacement checks compare with: the owned atoms' by the kernel itself, ghosts by a copy
             A.snap_dst = pos_snap_in.p;
             if (n_ghost > 0) MHIP_HIP(hipMemcpyAsync(pos_snap_in.p + n_owned, pos[cur].p + n_owned, (size_t)n_ghost * sizeof(T4), hipMemcpyDeviceToDevice, stream));
-            last_prune_step = pass_step;
+            lp.last_prune_step = pass_step;
             tile_idx_in.reserve((size_t)n_blocks * T_cap); tile_cnt_in.reserve(n_blocks);
             A.tile_idx_dst = tile_idx_in.p; A.tile_cnt_dst = tile_cnt_in.p;
             inner_is_outer = false;
@@ -1136,7 +1077,7 @@ template <class T> class Engine final : public EngineBase {
                                    reinterpret_cast<unsigned int*>(flags.p + FLAG_MAX_DISP2), G);
                 MHIP_HIP(hipMemcpyAsync(h_dst, flags.p, N_FLAGS * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
             }
-            ++n_filters; ghost_flags_in_ok = false; next_check_step = -1; hx.tile_ok = false; hx.trk_step = -1;
+            ++n_filters; ghost_flags_in_ok = false; lp.next_check_step = -1; hx.tile_ok = false; hx.trk_step = -1;
             inner_valid = true;
             if (late) {
                 MHIP_HIP(hipEventRecord(ev_prune, stream));
@@ -1147,8 +1088,8 @@ template <class T> class Engine final : public EngineBase {
                 prune_pending = false;
                 float d2; std::memcpy(&d2, &h_flags[FLAG_MAX_DISP2], sizeof(float));
                 total_rows = h_flags[FLAG_TOTAL_ROWS]; max_tile_in = h_flags[FLAG_MAX_TILE];
-                prune_disp_exceeded = 2.0 * std::sqrt((double)d2) > prune_margin() * 0.98;
-                if (debug_on) std::fprintf(stderr, "[mhip] prune: max disp %.5f nm (margin %.3f) rows %lld exceeded %d calls %lld\n", std::sqrt((double)d2), prune_margin(), (long long)total_rows, (int)prune_disp_exceeded, (long long)n_force_calls);
+                prune_disp_exceeded = !lp.prune_stands(std::sqrt((double)d2));
+                if (debug_on) std::fprintf(stderr, "[mhip] prune: max disp %.5f nm (margin %.3f) rows %lld exceeded %d calls %lld\n", std::sqrt((double)d2), lp.prune_margin(), (long long)total_rows, (int)prune_disp_exceeded, (long long)n_force_calls);
             }
         }
         return res;
@@ -1247,12 +1188,12 @@ template <class T> class Engine final : public EngineBase {
     bool halo_fused_ok(int64_t step_n) {
         if (!(xf_direct && xf.n_peers > 0 && n_ghost > 0 && hp_set && xf.routes) || replan_now) return false;
         if (hp.cm_rows != 3 || hp.n_cm_peers != xf.n_peers || (int)xf.peer_rank.size() != xf.n_peers) return false;
-        if (check_due(step_n, rebuild_every()) && step_n != last_build_step && !(host_prune && inner_valid)) return false;      // (refresh() of such a step only books it)
+        if (lp.check_due(step_n, rebuild_every()) && step_n != last_build_step && !(host_prune && inner_valid)) return false;      // (refresh() of such a step only books it)
         return packed_step_possible();
     }
     void halo_fused(int64_t step_n, double dt, bool cm, bool measure) {
-        cur_dt = dt;
-        if (check_due(step_n, rebuild_every()) && step_n != last_build_step && dual) refresh(step_n);
+        lp.cur_dt = dt;
+        if (lp.check_due(step_n, rebuild_every()) && step_n != last_build_step && dual) refresh(step_n);
         PassReq req;
         req.step = true; req.cm = cm; req.measure = measure; req.dt = dt; req.halo = true; req.halo_cm_in = halo_cm_in;
         const PassRes res = step_forces(step_n, req);
@@ -1289,9 +1230,9 @@ template <class T> class Engine final : public EngineBase {
         gs_balance();
         prof.end(4, stream);
         MHIP_HIP(hipGetLastError());
-        inner_is_outer = true; max_tile_in = max_tile; last_prune_step = pass_step;
+        inner_is_outer = true; max_tile_in = max_tile; lp.last_prune_step = pass_step;
         ++n_filters; ++n_adopted; gs_list_id = n_filters;
-        ghost_flags_in_ok = false; next_check_step = -1; hx.tile_ok = false;
+        ghost_flags_in_ok = false; lp.next_check_step = -1; hx.tile_ok = false;
         inner_valid = true; prune_disp_exceeded = false;
         if (debug_on) std::fprintf(stderr, "[mhip] outer list adopted as the inner list (no prune): rows %lld calls %lld\n", (long long)total_rows, (long long)n_force_calls);
     }
@@ -1339,12 +1280,6 @@ template <class T> class Engine final : public EngineBase {
     void stamps_dump(const char*, size_t) {}
     void stamps_report() {}
 #endif
-    // How far atoms may have moved since the outer search for a prune to be trustworthy: the outer list holds every pair within
-    // r_list + outer_margin of then, the prune wants every pair within rc_max + skin_in of now.
-    double prune_margin() const { return outer_margin + (skin - skin_in); }
-
-    const bool inner_skin_fixed = env_int("MOLLYHIP_INNER_SKIN_FIXED", 0) != 0;
-
     double read_sum(int n_part) {
         hipLaunchKernelGGL(k_sum_double, dim3(1), dim3(256), 0, stream, n_part, (const double*)red_part.p, red_out.p);
         MHIP_HIP(hipMemcpyAsync(h_red, red_out.p, sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -1586,14 +1521,14 @@ template <class T> class Engine final : public EngineBase {
         vel_check_due = vel_check_due || vel_new;
         if (dual) {
             const double d_outer = std::sqrt((double)max_disp2_since(pos_snap));
-            if (!(2.0 * d_outer <= prune_margin() * 0.98)) { stale = true; return; }
+            if (!lp.prune_stands(d_outer)) { stale = true; return; }
             if (inner_valid) {
                 const double d_in = std::sqrt((double)max_disp2_since(pos_snap_in));
-                if (!(2.0 * d_in <= skin_in * 0.98)) inner_valid = false;   // the next force pass re-prunes the outer list
+                if (!ListPolicy::covered(d_in, 0.0, lp.skin_in)) inner_valid = false;   // the next force pass re-prunes the outer list
             }
         } else {   // lazy_single: one list of radius r_list, snapshot of its build in pos_snap_in
             const double d = std::sqrt((double)max_disp2_since(pos_snap_in));
-            if (!(2.0 * d <= skin * 0.98)) stale = true;
+            if (!ListPolicy::covered(d, 0.0, lp.skin)) stale = true;
             else if (d > 0) export_needs_search = true;    // fine for forces; mhip_export_neighbors wants the list of the new coordinates
         }
         if (stale || !inner_valid) ++n_set_state_refresh;
@@ -1614,7 +1549,7 @@ template <class T> class Engine final : public EngineBase {
     }
 
     void forces(int64_t step_n, int accumulate, void* f_xyz, int mem_kind) override {
-        cur_dt = 0;   // driven from outside: no time step to bound the drift with
+        lp.cur_dt = 0;   // driven from outside: no time step to bound the drift with
         ensure_built(step_n);
         pass_step = step_n;
         launch_pair_kernel(false);
@@ -1863,7 +1798,7 @@ template <class T> class Engine final : public EngineBase {
         if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no constraints: use mhip_vv_run"};
         if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no virtual sites: use mhip_vv_run"};
         if (!frc_valid) throw ApiError{MHIP_ERR_STATE, "vv_stage1 needs forces from vv_init / vv_stage2"};
-        cur_dt = dt;
+        lp.cur_dt = dt;
         tr("k_vv1");
         prof.begin(2, stream);
         hipLaunchKernelGGL(k_vv1<T>, dim3(std::min(cdiv(n_owned, 256), 1024)), dim3(256), 0, stream, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, T(dt), T(dt) / T(2),
@@ -1890,7 +1825,7 @@ template <class T> class Engine final : public EngineBase {
     // (set_atom_counts / set_state → stale) by the host at every rebuild step instead.
     void stage2_cadenced(int64_t step_n, double dt, bool cm, double* cm_parts_ext = nullptr, int n_parts_ext = 0) {
         resolve_track(step_n);
-        const bool due = check_due(step_n, rebuild_every()) && step_n != last_build_step && (n_ghost == 0 || dual);
+        const bool due = lp.check_due(step_n, rebuild_every()) && step_n != last_build_step && (n_ghost == 0 || dual);
         if (due && dual) refresh(step_n);
         stage2_impl(step_n, dt, cm, cm_parts_ext, n_parts_ext);
         if (due && !dual) refresh(step_n);
@@ -1962,31 +1897,25 @@ template <class T> class Engine final : public EngineBase {
     // that nothing waits for them): the drift bounds then reach that much further
     int plan_decide_late(int64_t step_n, const float* red3, int32_t* check_in, int late) {
         if (check_in) *check_in = 0;
-        const int every = rebuild_every();
         if (!engine_sched) {   // first use: from now on the inner list may be tighter than r_list
             engine_sched = true;
-            skin_in = std::min(skin, inner_skin_floor());
-            const T rp = T(rc_max_ + skin_in);
-            r_prune2 = (skin_in < skin) ? rp * rp : r_in2;
+            lp.start_inner_skin(true, inner_skin_floor(), false);
+            set_prune_radius();
         }
         if (!dual || stale || std::isinf(red3[0])) return 2;
-        prev_vmax = last_vmax; last_vmax = std::sqrt((double)red3[2]);
-        ++n_disp_checks;
-        bool reprune = !inner_valid || std::isinf(red3[1]);
-        if (!reprune) {
-            // (measured at step_n, applied `late` steps later; the list is walked up to the pass of step_n + every — the next check's own step — as in resolve_track)
-            const double d = std::sqrt((double)red3[1]), ahead = drift_ahead(d, step_n - last_prune_step, every + std::max(late - 1, 0));
-            adapt_inner_skin(ahead);
-            reprune = !inner_valid || 2.0 * (d + ahead) > skin_in * 0.98;
-            // not good for a whole interval, but for k steps: the host looks again then (it owns the step loop)
-            if (reprune && inner_valid && check_in)
-                if (const int k = steps_within(d, 0.49 * skin_in, step_n - last_prune_step, every, true)) { if (k > late + 1) { *check_in = k; return 0; } }
+        lp.measured(std::sqrt((double)red3[2]));
+        // (measured at step_n, applied `late` steps later; the list is walked up to the pass of step_n + every — the next check's own step — as in resolve_track;
+        // not good for a whole interval, but for k steps: the host looks again then, it owns the step loop; a prune runs inside the NEXT force pass, one step
+        // from now (+ late): the outer test leaves it that much headroom)
+        const ListPolicy::Measured m{inner_valid ? std::sqrt((double)red3[1]) : (double)INFINITY, std::sqrt((double)red3[0]), step_n - lp.last_prune_step};
+        const ListPolicy::Decision r = lp.decide(m, ListPolicy::Applied::collective(rebuild_every(), step_n, late, check_in != nullptr, n_ghost > 0));
+        if (r.grown) inner_skin_grown(r.ahead);
+        switch (r.action) {
+        case ListPolicy::KEEP: return 0;
+        case ListPolicy::LOOK_AGAIN: *check_in = r.k; return 0;
+        case ListPolicy::PRUNE: inner_valid = false; return 1;
+        default: return 2;
         }
-        if (!reprune) return 0;
-        // the prune runs inside the NEXT force pass, one step from now (+ late): leave it that much headroom
-        if (2.0 * (std::sqrt((double)red3[0]) + last_vmax * cur_dt * 1.25 * (1 + late)) > prune_margin() * 0.98) return 2;
-        inner_valid = false;
-        return 1;
     }
 
     // ---- one MD step of a ghosted sub-domain in ONE call after the ghost exchange (fused integrator, Σ m v on the ghost message) --------
@@ -2043,9 +1972,9 @@ template <class T> class Engine final : public EngineBase {
             hipLaunchKernelGGL(k_halo_unpack<T>, dim3(cdiv(hp.n_recv_rows, 256)), dim3(256), 0, stream, hp.n_recv_rows, W.n_peers > 0 ? (const T*)xf_rows(W.parity) : (const T*)hp.recv, hp.recv_dst, hp.first_ghost, (const int32_t*)inv.p,
                                pos[cur].p, cm_all.p, std::max(hp.cm_rows, 1), W);
         }
-        cur_dt = dt;
+        lp.cur_dt = dt;
         if (replan_now) { replan_now = false; device_replan(step_n); }            // (mhip_domain_run: ownership, ghosts and the outer list redone here, in front of the step's force pass)
-        const bool due = check_due(step_n, rebuild_every()) && step_n != last_build_step && (n_ghost == 0 || dual);
+        const bool due = lp.check_due(step_n, rebuild_every()) && step_n != last_build_step && (n_ghost == 0 || dual);
         if (due && dual) refresh(step_n);
         const bool solo = hp.n_cm_peers == 0 && hp.n_send_rows == 0;              // no peers: the partials of the launch before are the whole sum
         // … which workgroup 0 of the pair pass in between adds up into ONE partial, as inside mhip_vv_run (ForceArgs::cm_fin_in): the integrator's blocks
@@ -2244,19 +2173,18 @@ template <class T> class Engine final : public EngineBase {
             // launches), with the lists kept by the engine's own criteria.  The run's last Σ m v goes to cm_parts_dev for the caller's (one-rank) sum.
             if (host_prune) {      // (set_ghost_margin handed the prune decisions to a host that has no peers to agree with)
                 host_prune = false; engine_sched = true;
-                skin_in = std::min(skin, std::max(skin_in_adapted, inner_skin_floor()));
-                const T rp = T(rc_max_ + skin_in);
-                r_prune2 = (skin_in < skin) ? rp * rp : r_in2;
+                lp.start_inner_skin(true, inner_skin_floor());
+                set_prune_radius();
                 inner_valid = false;
             }
-            cur_dt = dt;
-            const int64_t c0 = n_disp_checks, f0 = n_filters, o0 = n_outer;
+            lp.cur_dt = dt;
+            const int64_t c0 = lp.n_disp_checks, f0 = n_filters, o0 = n_outer;
             xf.plan_pending = false;
             vv_loop(first_step, n_steps, dt, remove_cm_every, cm_parts_dev, n_parts);
             flush_cm();
             *steps_done = n_steps;
             // (checks: those read so far + the one a launch has measured and the next call's first step will read)
-            if (counters) { counters[0] += n_disp_checks - c0 + (trk_issued ? 1 : 0); counters[1] += n_filters - f0; counters[2] += n_outer - o0; }
+            if (counters) { counters[0] += lp.n_disp_checks - c0 + (trk_issued ? 1 : 0); counters[1] += n_filters - f0; counters[2] += n_outer - o0; }
             dom.n_replans += n_outer - o0;
             MHIP_HIP(hipGetLastError());
             MHIP_HIP(hipStreamSynchronize(stream));
@@ -2563,7 +2491,7 @@ template <class T> class Engine final : public EngineBase {
     void vv_run(int64_t first_step, int64_t n_steps, double dt, int remove_cm_every) override {
         if (!state_set || !params_set) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before vv_run"};
         if (n_ghost > 0) throw ApiError{MHIP_ERR_STATE, "vv_run is single-domain; drive ghosted domains with vv_stage1/vv_stage2"};
-        cur_dt = dt;
+        lp.cur_dt = dt;
         InRun guard_in_run(in_run);
         sites_run_start();                                                        // :561-562
         if (first_step == 0 && remove_cm_every != 0) remove_cm();                 // simulators.jl:563
@@ -2604,27 +2532,27 @@ template <class T> class Engine final : public EngineBase {
             // scheduled before the force pass so that, with the dual pair list, that pass can prune the outer list on the way.
             // Forces are unaffected: the pass walks a superset of the old list and every interaction has a cutoff <= r_list.
             if (trk_issued && step > trk_step) resolve_track(step);
-            if (pre && check_due(step, every)) refresh(step);
+            if (pre && lp.check_due(step, every)) refresh(step);
             const bool cm = remove_cm_every != 0 && step % remove_cm_every == 0;
             if (!fused) {
                 stage2_impl(step, dt, cm);                                        // :612-628
                 apply_coupling(step);                                             // :630
-                if (!pre && check_due(step, every)) refresh(step);
+                if (!pre && lp.check_due(step, every)) refresh(step);
                 continue;
             }
             // the validity check of step + 1 is measured where its coordinates are made: by this step's integrator launch — or by the pair pass itself when it integrates
-            const bool measure = step != last && async_ok() && !trk_issued && check_due(step + 1, every);
+            const bool measure = step != last && async_ok() && !trk_issued && lp.check_due(step + 1, every);
             const bool integrate = step != last && !items_on();
             PassReq req;
             req.step = integrate && !bonded.any() && !pme.on(); req.cm = cm;      // (one kernel either way: its stage time is its own, so the stage timers leave it fused)
-            req.gcv = integrate && bonded.any() && pme.on() && (pre || !check_due(step, every));      // (a re-sort behind the pass would want the total force array)
+            req.gcv = integrate && bonded.any() && pme.on() && (pre || !lp.check_due(step, every));      // (a re-sort behind the pass would want the total force array)
             req.measure = measure; req.dt = dt;
             const PassRes res = step_forces(step, req);
             if (res.step) {      // the pair pass integrated on the way (k_forces STEP): no integrator launch for this step
                 after_fused_step(res, measure, step + 1, cm);
                 continue;
             }
-            if (!pre && check_due(step, every)) { fold_side_forces(); refresh(step); }   // the sort permutes vel / frc with the atoms; Σ m v does not care
+            if (!pre && lp.check_due(step, every)) { fold_side_forces(); refresh(step); }   // the sort permutes vel / frc with the atoms; Σ m v does not care
             // every block re-sums the previous step's per-block Σ m v partials (32 bytes each), so fewer, longer blocks pay: 1024 blocks
             // re-read 32 MB from L2 per launch — more than the 21 MB of atoms of the 256k-atom fluid (13.0 → 10.0 µs with 256 blocks;
             // 1M atoms: 21.2 → 20.2 µs with 512, 21.8 with 256)
@@ -2633,7 +2561,7 @@ template <class T> class Engine final : public EngineBase {
             double* cm_out = cm ? (parts_out ? cm_parts_last : cm_step.p + (size_t)half * 4 * 1024) : (double*)nullptr;
             prof.begin(2, stream);
             // the speeds for a check that the next step's force pass will measure (see resolve_track); evaluated behind the pass: a prune inside it makes the lists checkable again
-            const bool measure_mid = step != last && async_ok() && !trk_issued && check_due(step + 1, every);
+            const bool measure_mid = step != last && async_ok() && !trk_issued && lp.check_due(step + 1, every);
             if (measure_mid) trk_reserve(n_blocks);
             if (items_on()) con_launch(step == last ? 2 : 1, nb, dt, cm_out, measure_mid, nullptr);
             else vv_mid_launch(cm, step == last, nb, dt, pending_cm.parts_arg(), pending_cm.n, cm_out, measure_mid);
@@ -2839,7 +2767,7 @@ template <class T> class Engine final : public EngineBase {
         if (n_ghost > 0) throw ApiError{MHIP_ERR_STATE, "langevin_run is single-domain"};
         if (!(kT >= 0) || !(friction >= 0)) throw ApiError{MHIP_ERR_INVALID, "temperature and friction must be non-negative"};
         const int every = rebuild_every();
-        cur_dt = dt;
+        lp.cur_dt = dt;
         InRun guard_in_run(in_run);
         sites_run_start();                                                        // :1113-1114
         const bool items = items_on();                                            // constraints or hosted sites: both stepped by k_con_step
@@ -2861,14 +2789,14 @@ template <class T> class Engine final : public EngineBase {
             P.ctr1 = ctr1_0 + (uint64_t)(step - first_step - 1);
             // a small system's step (bonded terms + PME): its last force launch — interpolation + bonded sums — runs the update as well (step_fused.h, k_gather_collect_vv<…, LANG>),
             // every step of the run: a Langevin step is complete in itself, there is no closing half kick to keep a launch for
-            const bool measure = in_lang_async && async_ok() && !trk_issued && check_due(step, every);      // the check refresh(step) below would make with a drained stream
+            const bool measure = in_lang_async && async_ok() && !trk_issued && lp.check_due(step, every);      // the check refresh(step) below would make with a drained stream
             PassReq req;
             req.gcv = bonded.any() && pme.on() && !items; req.step = !bonded.any() && !pme.on() && !items; req.lang = &P; req.cm = cm; req.measure = measure; req.dt = dt;      // (step: the packed fp32 one-type pass runs the update in its epilogue, k_forces<…, STEP, ·, LANG>)
             const PassRes res = step_forces(step, req);                          // :1173
             if (res.step) {
                 after_fused_step(res, measure, step, cm);
                 apply_coupling(step);
-                if (check_due(step, every)) refresh(step);
+                if (lp.check_due(step, every)) refresh(step);
                 continue;
             }
             prof.begin(2, stream);
@@ -2885,7 +2813,7 @@ template <class T> class Engine final : public EngineBase {
             pend_a = nullptr; pending_cm.none(); frc_valid = false;
             if (cm) { pending_cm.resum(cm_out, nb); half ^= 1; }   // :1204-1206, subtracted by the next consumer
             apply_coupling(step);                                                 // :1208
-            if (check_due(step, every)) refresh(step);                            // :1211 — the next force pass prunes the fresh outer list
+            if (lp.check_due(step, every)) refresh(step);                            // :1211 — the next force pass prunes the fresh outer list
         }
         flush_cm();
         if (items) con_read_back();
@@ -2903,7 +2831,7 @@ template <class T> class Engine final : public EngineBase {
             if (!state_set || !params_set) throw ApiError{MHIP_ERR_STATE, "no neighbour list: call set_atoms and set_state first"};
             flush_cm(); rebuild(last_build_step == std::numeric_limits<int64_t>::min() ? 0 : last_build_step);
         }
-        if (now && lazy_single && (last_build_step != last_prune_step || export_needs_search)) { flush_cm(); rebuild(last_build_step); }   // skipped rebuilds / moved coordinates: hand out the list of NOW
+        if (now && lazy_single && (last_build_step != lp.last_prune_step || export_needs_search)) { flush_cm(); rebuild(last_build_step); }   // skipped rebuilds / moved coordinates: hand out the list of NOW
         const int32_t *x_tidx = tile_idx.p, *x_tcnt = tile_cnt.p, *x_rows = wave_rows.p; const uint2* x_nbr = nbr.p;
         if (dual) {
             // the reference's list at the current coordinates = the outer list filtered with the exact predicate; valid as long as
@@ -2913,7 +2841,7 @@ template <class T> class Engine final : public EngineBase {
                 MHIP_HIP(hipMemcpyAsync(h_flags, flags.p, N_FLAGS * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
                 MHIP_HIP(hipStreamSynchronize(stream));
                 float d2; std::memcpy(&d2, &h_flags[FLAG_MAX_DISP2], sizeof(float));
-                if (2.0 * std::sqrt((double)d2) <= outer_margin * 0.98 || !now) break;
+                if (ListPolicy::covered(std::sqrt((double)d2), 0.0, lp.outer_margin) || !now) break;
                 flush_cm(); rebuild(last_build_step);
                 if (!dual) break;
             }
