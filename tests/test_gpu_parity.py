@@ -292,25 +292,25 @@ def test_nve_energy_conservation_short(pkg):
 
 
 def test_bonded_terms_match_oracle(pkg):
-    # a synthetic 60-bead chain with bonds, angles, torsions (2 Fourier terms each) and Ewald exclusions
-    rng = np.random.default_rng(6)
-    n = 60
-    x = np.cumsum(rng.normal(size=(n, 3)) * 0.09 + np.array([0.08, 0.02, 0.01]), axis=0) + 3.0
-    idx = np.arange(n)
-    bonds = dict(i=idx[:-1], j=idx[1:], k=np.full(n - 1, 250000.0), r0=np.full(n - 1, 0.15))
-    angles = dict(i=idx[:-2], j=idx[1:-1], k=idx[2:], kth=np.full(n - 2, 400.0), th0=np.full(n - 2, 1.9))
-    ti = np.repeat(idx[:-3], 2)
-    tors = dict(i=ti, j=ti + 1, k=ti + 2, l=ti + 3, periodicity=np.tile([1, 3], n - 3), phase=np.tile([0.0, math.pi], n - 3), k0=np.tile([2.5, 0.7], n - 3))
-    ewx = np.concatenate([np.stack([idx[:-1], idx[1:]], 1), np.stack([idx[:-2], idx[2:]], 1)])
-    q = rng.normal(size=n) * 0.4
-    case = S.Case(x, 8.0, coul=dict(kind="ewald", rc=1.0), r_list=1.2, charge=q, excluded=ewx, bonds=bonds, angles=angles, torsions=tors, ewald_excl=ewx)
-    for dtype, rtol in ((np.float64, 1e-9), (np.float32, 3e-4)):
+    # a synthetic 60-bead chain with bonds, angles, torsions (2 Fourier terms each) and Ewald exclusions (tests/bonded_ref.py: bead_chain).  Per atom against
+    # S_i = Σ over its terms of the norm of the term's force on it — 1e-9·S_i in fp64, twice the fp32 oracle's own loss in fp32 (test_bonded_host.YARD32) — AND
+    # the former bar against the largest force component, so that no atom's bar got looser: the chain's largest force is a bond force of 1e4 kJ/mol/nm, three
+    # hundred times its torsion forces.
+    from tests import bonded_ref as R
+    from tests.test_bonded_host import YARD32
+    case = R.bead_chain()
+    scale = R.per_atom_scale(case)
+    assert np.all(scale > 0)
+    for dtype, rtol, bar in ((np.float64, 1e-9, 1e-9), (np.float32, 3e-4, 2.0 * YARD32["bead_all"][0])):
         o = case.oracle(np.float64)
         f_ref = o.forces(None, pairwise=False, specific=True)
         e_ref = o.potential_energy(None, pairwise=False, specific=True)
         s = case.system(pkg, dtype)
         f = pkg.forces(s, pairwise=False)
         assert np.abs(f - f_ref).max() <= rtol * np.abs(f_ref).max()
+        ratio = np.linalg.norm(f.astype(np.float64) - f_ref, axis=1) / scale
+        print(f"[bonded] bead chain {np.dtype(dtype).name}: worst ‖Δf_i‖/S_i {ratio.max():.3e} (bar {bar:.3e})")
+        assert ratio.max() <= bar, (ratio.max(), int(ratio.argmax()))
         assert pkg.potential_energy(s, pairwise=False) == pytest.approx(e_ref, rel=max(rtol, 1e-9))
 
 
