@@ -296,6 +296,23 @@ int32_t mhip_andersen(mhip_ctx* ctx, double kT, double prob, uint64_t philox_key
 /* The same thermostat as the `coupling` of mhip_vv_run / mhip_langevin_run: applied after every step's CM removal (simulators.jl:630,
  * 1208); the per-step (ctr1, key) are words of philox(step, 0; seed).  prob <= 0 switches it off. */
 int32_t mhip_set_andersen(mhip_ctx* ctx, double kT, double prob, uint64_t seed);
+/* The rescaling thermostats as the `coupling` of mhip_vv_run — a uniform v *= λ, λ from the kinetic energy of the moment, computed and applied on
+ * the device with no read-back inside the run.
+ * kind 0 off | 1 ImmediateThermostat | 2 BerendsenThermostat | 3 VelocityRescaleThermostat (coupling.jl:68-238);
+ * kT = k·temperature [kJ/mol], coupling_const [ps], dof = sys.df; kinds 1, 2: n_steps must be 1.
+ * Applied by mhip_vv_run at the end of every step s with s % n_steps == 0, behind that step's CM removal (simulators.jl:627-643);
+ * kind 3 draws from (philox_key, philox_ctr1 + s): atom i owns the three normals mhip_random_velocities would draw for it, numbered k = 3i + c;
+ * R is k = 0, S the sum of the squares of 1 <= k <= dof − 1.  dof <= 0 or K <= 0 leaves the velocities alone (λ = 1), as does a negative λ² of
+ * kinds 1 and 2 (the reference's sqrt domain error).  Constraints, virtual sites, bonded terms, PME, a TriclinicBoundary and both precisions are
+ * supported: a uniform scale commutes with RATTLE.  MHIP_ERR_INVALID for a kind outside 0..3, kT, coupling_const or n_steps not positive, n_steps != 1
+ * for kinds 1 and 2; MHIP_ERR_UNSUPPORTED next to the Andersen coupling, with ghosts or a domain plan (in either call order); the split step, the halo
+ * entry points (mhip_set_halo_plan, mhip_vv_halo_start / _mid / _begin / _end / _end_parts, each with a check of its own), mhip_set_domain,
+ * mhip_domain_run and mhip_langevin_run refuse a context with a thermostat set.  Kind 0 restores a context that never had one. */
+int32_t mhip_set_thermostat(mhip_ctx* ctx, int32_t kind, double kT, double coupling_const, int32_t n_steps, int64_t dof,
+                            uint64_t philox_key, uint64_t philox_ctr1);
+/* out[8]: applications since set; step of the last one; its λ; its K before scaling [kJ/mol]; smallest and largest λ since set;
+ * applications refused (negative λ², K <= 0); spare.  Written on the device, copied with the run's closing synchronisation. */
+int32_t mhip_thermostat_info(mhip_ctx* ctx, double* out8);
 /* the raw generator on the device (known-answer tests): out4 = philox4x32_10(ctr4, key2) */
 int32_t mhip_philox4x32_10(const uint32_t* ctr4, const uint32_t* key2, uint32_t* out4);
 

@@ -240,12 +240,15 @@ function push_specific!(c::HipContext, sys::System{3, <:ROCArray, T}) where T
 end
 
 # The run is cut where something on the host side is due: a logger (its n_steps; apply_loggers! fires at the multiples, simulators.jl:657) or a coupling the engine does not
-# carry — every coupling of coupling.jl except the AndersenThermostat, which is the engine's (mhip_set_andersen).  Those are applied by the reference's own
+# carry.  The engine's own: the AndersenThermostat (mhip_set_andersen) and, under HIPVelocityVerlet, the three rescaling thermostats (mhip_set_thermostat: λ is computed
+# and applied inside the device loop, no cut).  The others are applied by the reference's own
 # apply_coupling! between two chunks (coordinates, velocities and the boundary go back to the engine behind it; context! follows a replaced boundary: mhip_set_box), at
-# the multiples of their n_steps where they have one (MonteCarloBarostat) and after every step where they have not (the rescaling thermostats); couplings that read the
-# virial of their step's force call are refused below.
+# the multiples of their n_steps where they have one (MonteCarloBarostat) and after every step where they have not (the rescaling thermostats under HIPLangevin); couplings
+# that read the virial of their step's force call are refused below.
+const RescalingThermostat = Union{ImmediateThermostat, BerendsenThermostat, VelocityRescaleThermostat}
 couplers_of(sim) = sim.coupling === nothing ? () : (sim.coupling isa Union{Tuple, NamedTuple} ? Tuple(values(sim.coupling)) : (sim.coupling,))
-host_couplers(sim) = Tuple(c for c in couplers_of(sim) if !(c isa AndersenThermostat))
+engine_coupler(sim, c) = c isa AndersenThermostat                                    # (HIPVelocityVerlet adds the rescaling thermostats below)
+host_couplers(sim) = Tuple(c for c in couplers_of(sim) if !engine_coupler(sim, c))
 host_intervals(sys, sim) = (Int[l.n_steps for l in values(sys.loggers) if hasproperty(l, :n_steps)]..., Int[hasproperty(c, :n_steps) ? c.n_steps : 1 for c in host_couplers(sim)]...)
 next_stop(first, last, intervals) = minimum((last, ((fld(first, k) + 1) * k for k in intervals if k > 0)...))
 
@@ -281,6 +284,29 @@ end
 struct HIPVelocityVerlet{T, C}; dt::T; coupling::C; remove_CM_motion::Int; end
 HIPVelocityVerlet(; dt, coupling=nothing, remove_CM_motion=1) = HIPVelocityVerlet(dt, coupling, Int(remove_CM_motion))   # ≙ VelocityVerlet, simulators.jl:280-300
 
+engine_coupler(sim::HIPVelocityVerlet, c) = c isa Union{AndersenThermostat, RescalingThermostat}
+
+# coupling.jl:68-238 inside mhip_vv_run: kind, kT, τ, n_steps, dof = sys.df and the Philox (key, ctr1) drawn once per call; application s draws from (key, ctr1 + s)
+thermostat_kind(::ImmediateThermostat) = Int32(1)
+thermostat_kind(::BerendsenThermostat) = Int32(2)
+thermostat_kind(::VelocityRescaleThermostat) = Int32(3)
+function with_thermostat(f, c::HipContext, sys, sim, rng)
+    ths = Tuple(x for x in couplers_of(sim) if x isa RescalingThermostat)
+    isempty(ths) && return f()
+    length(ths) == 1 || error("MollyHIPExt: one rescaling thermostat per simulator")
+    th = ths[1]
+    tau = th isa ImmediateThermostat ? 1.0 : Float64(ustrip(u"ps", th.coupling_const))
+    n = th isa VelocityRescaleThermostat ? Int32(th.n_steps) : Int32(1)
+    check(c, ccall((:mhip_set_thermostat, libmollyhip), Int32, (Ptr{Cvoid}, Int32, Float64, Float64, Int32, Int64, UInt64, UInt64), c.ptr,
+                   thermostat_kind(th), Float64(ustrip(th.temperature * sys.k)), tau, n, Int64(sys.df), rand(rng, UInt64), rand(rng, UInt64)))
+    try
+        return f()
+    finally
+        ccall((:mhip_set_thermostat, libmollyhip), Int32, (Ptr{Cvoid}, Int32, Float64, Float64, Int32, Int64, UInt64, UInt64), c.ptr,
+              Int32(0), 0.0, 0.0, Int32(1), Int64(0), UInt64(0), UInt64(0))
+    end
+end
+
 function with_andersen(f, c::HipContext, sys, sim, rng)                              # coupling.jl:188-211: kT, P = dt/τ, per-step Philox words
     ths = Tuple(x for x in couplers_of(sim) if x isa AndersenThermostat)
     isempty(ths) && return f()
@@ -299,9 +325,11 @@ function simulate!(sys::System{3, <:ROCArray, T}, sim::HIPVelocityVerlet, n_step
                    init_step::Integer=0, run_loggers=true, rng=Random.default_rng(), kwargs...) where T
     c = context!(sys)
     with_andersen(c, sys, sim, rng) do
-        run_chunks!(c, sys, sim, n_steps, init_step, run_loggers, rng) do first, n   # ≙ simulators.jl:589-666
-            check(c, ccall((:mhip_vv_run, libmollyhip), Int32, (Ptr{Cvoid}, Int64, Int64, Float64, Int32),
-                           c.ptr, Int64(first), Int64(n), Float64(ustrip(sim.dt)), Int32(sim.remove_CM_motion)))
+        with_thermostat(c, sys, sim, rng) do
+            run_chunks!(c, sys, sim, n_steps, init_step, run_loggers, rng) do first, n   # ≙ simulators.jl:589-666
+                check(c, ccall((:mhip_vv_run, libmollyhip), Int32, (Ptr{Cvoid}, Int64, Int64, Float64, Int32),
+                               c.ptr, Int64(first), Int64(n), Float64(ustrip(sim.dt)), Int32(sim.remove_CM_motion)))
+            end
         end
     end
 end

@@ -125,6 +125,8 @@ SIGNATURES = {
     "mhip_random_velocities": (_I32, [_P, _D, C.c_uint64, C.c_uint64]),
     "mhip_andersen": (_I32, [_P, _D, _D, C.c_uint64, C.c_uint64]),
     "mhip_set_andersen": (_I32, [_P, _D, _D, C.c_uint64]),
+    "mhip_set_thermostat": (_I32, [_P, _I32, _D, _D, _I32, _I64, C.c_uint64, C.c_uint64]),
+    "mhip_thermostat_info": (_I32, [_P, C.POINTER(_D)]),
     "mhip_philox4x32_10": (_I32, [_P, _P, _P]),
     "mhip_specific_virial": (_I32, [_P, _P]),
     "mhip_general_virial": (_I32, [_P, _P]),

@@ -275,6 +275,31 @@ class AndersenThermostat:
     coupling_const: float
 
 
+@dataclass
+class ImmediateThermostat:
+    """ImmediateThermostat(temperature) (coupling.jl:68-91): every step the velocities are scaled by λ = sqrt(T₀ / T)."""
+    temperature: float
+
+
+@dataclass
+class BerendsenThermostat:
+    """BerendsenThermostat(temperature, coupling_const) (coupling.jl:214-238): λ² = 1 + (dt / coupling_const)·(T₀ / T − 1) every step."""
+    temperature: float
+    coupling_const: float
+
+
+@dataclass
+class VelocityRescaleThermostat:
+    """VelocityRescaleThermostat(temperature, coupling_const; n_steps=1) (coupling.jl:93-168): Bussi's stochastic velocity rescaling, applied every
+    n_steps steps with the time step dt·n_steps."""
+    temperature: float
+    coupling_const: float
+    n_steps: int = 1
+
+
+_RESCALE_KIND = {ImmediateThermostat: 1, BerendsenThermostat: 2, VelocityRescaleThermostat: 3}      # mhip_set_thermostat
+
+
 class Langevin:
     """Langevin(; dt, temperature, friction, coupling=nothing, remove_CM_motion=1) — the Langevin middle integrator
     (simulators.jl:1065-1097): vel_scale = exp(−dt·friction), noise_scale = sqrt(1 − vel_scale²)."""
@@ -618,6 +643,13 @@ class System:
         keys = ("clusters12", "clusters23", "clusters34", "angle_clusters", "n_constraints", "max_iters_last_run", "n_not_converged")
         return dict(zip(keys, list(out)[:7]))
 
+    def thermostat_info(self):
+        """mhip_thermostat_info: what the rescaling thermostat of the last coupled simulate did (written on the device, read with the run's end)"""
+        out = (C.c_double * 8)()
+        self._check(_lib.lib().mhip_thermostat_info(self.engine(), out))
+        keys = ("n_applied", "last_step", "last_lambda", "last_kinetic_energy", "min_lambda", "max_lambda", "n_refused")
+        return dict(zip(keys, list(out)[:7]))
+
     def _refuse_constrained(self, what):
         if self.constraints:
             raise MollyHipError(-6, f"{what} of a constrained System is not supported (the rigid-molecule treatment stays in Julia)")
@@ -738,9 +770,14 @@ def kinetic_energy(sys):
     return ke.value
 
 
+def _df(sys):
+    """sys.df = 3(N − n_sites) − 3 − n_constraints for a fully periodic box (constraints.jl:358-380, types.jl:957-959)"""
+    return 3 * (len(sys) - len(sys.virtual_sites)) - 3 - sys.n_constraints
+
+
 def temperature(sys):
-    """T = 2 KE / (df k), df = 3(N − n_sites) − 3 − n_constraints for a fully periodic box (energy.jl:158-175, constraints.jl:358-380, types.jl:957-959)."""
-    return 2 * kinetic_energy(sys) / ((3 * (len(sys) - len(sys.virtual_sites)) - 3 - sys.n_constraints) * BOLTZMANN)
+    """T = 2 KE / (df k) (energy.jl:158-175)."""
+    return 2 * kinetic_energy(sys) / (_df(sys) * BOLTZMANN)
 
 
 def total_energy(sys):
@@ -817,7 +854,8 @@ def _minimize(sys, sim, init_step=0):
 
 def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
     """simulate!(sys, sim, n_steps; init_step, rng) for VelocityVerlet (simulators.jl:547-668) and Langevin (:1099-1220), with
-    coupling nothing, AndersenThermostat, MonteCarloBarostat or a tuple of the two.  The step loop runs on the device; with a barostat it is cut at the
+    coupling nothing, AndersenThermostat, MonteCarloBarostat or a tuple of the two; VelocityVerlet also takes ImmediateThermostat, BerendsenThermostat and
+    VelocityRescaleThermostat (alone or with the barostat), applied inside the device loop.  The step loop runs on the device; with a barostat it is cut at the
     multiples of barostat.n_steps, where apply_coupling! runs on the host side of the boundary with the engine's potential energies (the README's GPU
     example: Langevin + MonteCarloBarostat).  Coordinates and velocities come back when the call returns.  rng: a numpy Generator or a seed; as in the
     reference it supplies the Philox key / counter words and the barostat's uniform numbers."""
@@ -832,10 +870,12 @@ def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
     if n_steps is None:
         raise TypeError("simulate: n_steps is required for VelocityVerlet and Langevin")
     couplings = sim.coupling if isinstance(sim.coupling, (tuple, list)) else (() if sim.coupling is None else (sim.coupling,))
-    thermostat = barostat = None
+    thermostat = barostat = rescale = None
     for c in couplings:
         if isinstance(c, AndersenThermostat) and thermostat is None:
             thermostat = c
+        elif type(c) in _RESCALE_KIND and rescale is None:
+            rescale = c
         elif isinstance(c, MonteCarloBarostat) and barostat is None:
             barostat = c
         else:
@@ -845,6 +885,10 @@ def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
     if barostat is not None:
         sys._refuse_constrained("MonteCarloBarostat coupling")
         sys._refuse_sites("MonteCarloBarostat coupling")
+    if rescale is not None and isinstance(sim, Langevin):
+        raise MollyHipError(-6, f"{type(rescale).__name__} is a coupling of VelocityVerlet, not of Langevin")
+    if rescale is not None and thermostat is not None:
+        raise MollyHipError(-6, f"{type(rescale).__name__} next to AndersenThermostat is not supported")
     if thermostat is not None and sys.virtual_sites:
         raise MollyHipError(-6, "AndersenThermostat coupling of a System with virtual sites is not supported")
     if thermostat is not None and sys.constraints:
@@ -855,6 +899,9 @@ def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
     if thermostat is not None:
         sys._check(L.mhip_set_andersen(sys._ctx, BOLTZMANN * float(thermostat.temperature), float(sim.dt) / float(thermostat.coupling_const), _rand_u64(rng)))
     try:
+        if rescale is not None:      # key and ctr1 once per call; application s draws from (key, ctr1 + s) on the device
+            sys._check(L.mhip_set_thermostat(sys._ctx, _RESCALE_KIND[type(rescale)], BOLTZMANN * float(rescale.temperature), float(getattr(rescale, "coupling_const", 1.0)),
+                                             int(getattr(rescale, "n_steps", 1)), _df(sys), _rand_u64(rng), _rand_u64(rng)))
         if isinstance(sim, Langevin):
             key, ctr1 = _rand_u64(rng), _rand_u64(rng)             # simulators.jl:1149-1150
         first, last = init_step, init_step + n_steps
@@ -873,6 +920,8 @@ def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
     finally:
         if thermostat is not None:
             sys._check(L.mhip_set_andersen(sys._ctx, 0.0, 0.0, 0))
+        if rescale is not None:
+            sys._check(L.mhip_set_thermostat(sys._ctx, 0, 0.0, 0.0, 1, 0, 0, 0))
     if check_nans:
         sys._check(L.mhip_check_finite(sys._ctx))
     if sys.constraints and sys.constraint_info()["n_not_converged"] > 0:        # shake.jl:817

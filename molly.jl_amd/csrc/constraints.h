@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "stochastic.h"
+#include "thermostat.h"
 #include "virtual_sites.h"
 
 namespace mhip {
@@ -76,6 +77,8 @@ template <class T> struct ConStep {
 // the next step's kick + RATTLE + drift + SHAKE (k_vv_mid's place); 2: closing kick + RATTLE, Σ m v (the run's last step); 3: the
 // Langevin step after the forces (k_langevin's place)
 template <class T>
-void launch_con_step(hipStream_t s, int n_blocks, int mode, const ConP<T>& C, const ConStep<T>& A, const GridP<T>& G);
+void launch_con_step(hipStream_t s, int n_blocks, int mode, const ConP<T>& C, const ConStep<T>& A, const GridP<T>& G, const ThermoArgs* X = nullptr);
+// X (nullable): a step on which a rescaling thermostat applies (thermostat_step.h), launched as k_con_thermo with one more kernel argument — mode 2 is its close launch
+// and leaves the thermostat partials in X->th_out, mode 0 its open launch and reads them (X->th_in) beside A.cm_in.  The uncoupled launches' arguments are what they were.
 
 }  // namespace mhip

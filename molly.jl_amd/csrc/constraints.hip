@@ -397,11 +397,13 @@ __device__ inline void sites_place(const ConP<T>& C, const ConStep<T>& A, const 
     }
 }
 
-struct Acc { double px = 0, py = 0, pz = 0, m = 0; float da = 0.f, db = 0.f, v2 = 0.f; int max_it = 0; int n_fail = 0; };
+struct Acc { double px = 0, py = 0, pz = 0, m = 0, mv2 = 0; float da = 0.f, db = 0.f, v2 = 0.f; int max_it = 0; int n_fail = 0; };
 
 // one work item: the arithmetic of k_vv1 / k_vv_mid / k_langevin per atom, with RATTLE after every kick and SHAKE after every drift
-template <class T, int K, int MODE>
-__device__ inline void con_item(const ConP<T>& C, const ConStep<T>& A, const GridP<T>& G, int64_t t, const T* vc, bool sub, const T* sh, Acc& acc) {
+// TH (a step on which a rescaling thermostat applies, thermostat_step.h): MODE 2 adds Σ m|v|² of the velocities it stores to acc, MODE 0 scales
+// v = lam·(v − v_cm) in front of the first kick
+template <class T, int K, int MODE, bool TH = false>
+__device__ inline void con_item(const ConP<T>& C, const ConStep<T>& A, const GridP<T>& G, int64_t t, const T* vc, bool sub, const T* sh, Acc& acc, T lam = T(1)) {
 #pragma clang fp contract(off)
     using T4 = typename Vec<T>::T4;
     constexpr int NA = Shape<K>::NA, NC = Shape<K>::NC;
@@ -414,7 +416,8 @@ __device__ inline void con_item(const ConP<T>& C, const ConStep<T>& A, const Gri
         id[k] = C.atoms[4 * t + k]; sl[k] = C.inv[id[k]];
         p[k] = A.pos[sl[k]]; v[k] = A.vel[sl[k]]; f[k] = A.frc[sl[k]];
         if (A.fa) { const T4 ga = A.fa[sl[k]]; f[k].x += ga.x; f[k].y += ga.y; f[k].z += ga.z; }
-        if (sub) {                                                             // remove_CM_motion! of the step before, one launch late
+        if constexpr (TH && MODE == 0) thermo_scale<T>(v[k], vc, sub, lam);      // remove_CM_motion! and the thermostat of the step this launch follows
+        else if (sub) {                                                        // remove_CM_motion! of the step before, one launch late
             v[k].x -= vc[0]; v[k].y -= vc[1]; v[k].z -= vc[2];
             if constexpr (MODE == 1 || MODE == 2) { p[k].x = M<T>::sub(p[k].x, sh[0]); p[k].y = M<T>::sub(p[k].y, sh[1]); p[k].z = M<T>::sub(p[k].z, sh[2]); }
         }
@@ -433,6 +436,9 @@ __device__ inline void con_item(const ConP<T>& C, const ConStep<T>& A, const Gri
         if (A.cm_out)
 #pragma unroll
             for (int k = 0; k < NA; ++k) { acc.px += (double)v[k].x * v[k].w; acc.py += (double)v[k].y * v[k].w; acc.pz += (double)v[k].z * v[k].w; acc.m += v[k].w; }
+        if constexpr (TH)
+#pragma unroll
+            for (int k = 0; k < NA; ++k) thermo_accum<T>(v[k], acc.mv2);
     }
     if constexpr (MODE != 2) {
 #pragma unroll
@@ -495,24 +501,27 @@ __device__ inline void con_item(const ConP<T>& C, const ConStep<T>& A, const Gri
     }
 }
 
-template <class T, int MODE>
-__global__ void __launch_bounds__(CON_BLOCK) k_con_step(ConP<T> C, ConStep<T> A, GridP<T> G) {
+template <class T, int MODE, bool TH>
+__device__ __forceinline__ void con_step_body(const ConP<T>& C, const ConStep<T>& A, const GridP<T>& G, const ThermoArgs& X) {
+    static_assert(!TH || MODE == 0 || MODE == 2, "the thermostat's launches: close (2) and open (0)");
     T vc[3] = {T(0), T(0), T(0)};
+    [[maybe_unused]] T lam = T(1);
     const bool sub = A.vcm != nullptr || A.cm_in != nullptr;
-    if (A.cm_in) block_vcm<T>(A.cm_in, A.n_cm_in, vc);
+    if constexpr (TH && MODE == 0) lam = thermo_block_lambda<T>(A.cm_in, X.th_in, A.n_cm_in, X.th, vc);      // (the open launch: cm_in, th_in are the close launch's partials)
+    else if (A.cm_in) block_vcm<T>(A.cm_in, A.n_cm_in, vc);
     else if (A.vcm) { vc[0] = A.vcm[0]; vc[1] = A.vcm[1]; vc[2] = A.vcm[2]; }
     const T sh[3] = {M<T>::mul(vc[0], A.dt), M<T>::mul(vc[1], A.dt), M<T>::mul(vc[2], A.dt)};
     Acc acc;
     const int64_t n = C.end[CK_N - 1], stride = (int64_t)gridDim.x * blockDim.x;      // (a multiple of the wave: a wave stays within one kind)
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += stride) {
-        if (t < C.end[CK_2]) con_item<T, CK_2, MODE>(C, A, G, t, vc, sub, sh, acc);
-        else if (t < C.end[CK_3]) con_item<T, CK_3, MODE>(C, A, G, t, vc, sub, sh, acc);
-        else if (t < C.end[CK_4]) con_item<T, CK_4, MODE>(C, A, G, t, vc, sub, sh, acc);
-        else if (t < C.end[CK_ANGLE]) con_item<T, CK_ANGLE, MODE>(C, A, G, t, vc, sub, sh, acc);
-        else if (t < C.end[CK_FREE]) con_item<T, CK_FREE, MODE>(C, A, G, t, vc, sub, sh, acc);
-        else if (t < C.end[CK_G2]) con_item<T, CK_G2, MODE>(C, A, G, t, vc, sub, sh, acc);
-        else if (t < C.end[CK_G3]) con_item<T, CK_G3, MODE>(C, A, G, t, vc, sub, sh, acc);
-        else con_item<T, CK_G4, MODE>(C, A, G, t, vc, sub, sh, acc);
+        if (t < C.end[CK_2]) con_item<T, CK_2, MODE, TH>(C, A, G, t, vc, sub, sh, acc, lam);
+        else if (t < C.end[CK_3]) con_item<T, CK_3, MODE, TH>(C, A, G, t, vc, sub, sh, acc, lam);
+        else if (t < C.end[CK_4]) con_item<T, CK_4, MODE, TH>(C, A, G, t, vc, sub, sh, acc, lam);
+        else if (t < C.end[CK_ANGLE]) con_item<T, CK_ANGLE, MODE, TH>(C, A, G, t, vc, sub, sh, acc, lam);
+        else if (t < C.end[CK_FREE]) con_item<T, CK_FREE, MODE, TH>(C, A, G, t, vc, sub, sh, acc, lam);
+        else if (t < C.end[CK_G2]) con_item<T, CK_G2, MODE, TH>(C, A, G, t, vc, sub, sh, acc, lam);
+        else if (t < C.end[CK_G3]) con_item<T, CK_G3, MODE, TH>(C, A, G, t, vc, sub, sh, acc, lam);
+        else con_item<T, CK_G4, MODE, TH>(C, A, G, t, vc, sub, sh, acc, lam);
     }
     // the solver's counters: one vector atomic per wave into device words the host reads with the run's other read-backs
     int mi = acc.max_it;
@@ -542,12 +551,24 @@ __global__ void __launch_bounds__(CON_BLOCK) k_con_step(ConP<T> C, ConStep<T> A,
         __syncthreads();
         if (threadIdx.x < 4) { double a = 0; for (int q = 0; q < (int)(blockDim.x >> 6); ++q) a += shm[q][threadIdx.x]; A.cm_out[4 * (int64_t)blockIdx.x + threadIdx.x] = a; }
     }
+    if constexpr (TH && MODE == 2) thermo_write_partial(acc.mv2, thermo_noise_share<T>(X.th), X.th_out);
 }
+
+template <class T, int MODE>
+__global__ void __launch_bounds__(CON_BLOCK) k_con_step(ConP<T> C, ConStep<T> A, GridP<T> G) { con_step_body<T, MODE, false>(C, A, G, ThermoArgs{}); }
+// the close (MODE 2) and open (MODE 0) launches of a step on which a rescaling thermostat applies (thermostat_step.h)
+template <class T, int MODE>
+__global__ void __launch_bounds__(CON_BLOCK) k_con_thermo(ConP<T> C, ConStep<T> A, GridP<T> G, ThermoArgs X) { con_step_body<T, MODE, true>(C, A, G, X); }
 
 }  // namespace
 
 template <class T>
-void launch_con_step(hipStream_t s, int nb, int mode, const ConP<T>& C, const ConStep<T>& A, const GridP<T>& G) {
+void launch_con_step(hipStream_t s, int nb, int mode, const ConP<T>& C, const ConStep<T>& A, const GridP<T>& G, const ThermoArgs* X) {
+    if (X) {      // a coupled step's close (2) and open (0)
+        if (mode == 2) hipLaunchKernelGGL((k_con_thermo<T, 2>), dim3(nb), dim3(CON_BLOCK), 0, s, C, A, G, *X);
+        else hipLaunchKernelGGL((k_con_thermo<T, 0>), dim3(nb), dim3(CON_BLOCK), 0, s, C, A, G, *X);
+        return;
+    }
     switch (mode) {
     case 0: hipLaunchKernelGGL((k_con_step<T, 0>), dim3(nb), dim3(CON_BLOCK), 0, s, C, A, G); break;
     case 1: hipLaunchKernelGGL((k_con_step<T, 1>), dim3(nb), dim3(CON_BLOCK), 0, s, C, A, G); break;
@@ -555,7 +576,7 @@ void launch_con_step(hipStream_t s, int nb, int mode, const ConP<T>& C, const Co
     default: hipLaunchKernelGGL((k_con_step<T, 3>), dim3(nb), dim3(CON_BLOCK), 0, s, C, A, G); break;
     }
 }
-template void launch_con_step<float>(hipStream_t, int, int, const ConP<float>&, const ConStep<float>&, const GridP<float>&);
-template void launch_con_step<double>(hipStream_t, int, int, const ConP<double>&, const ConStep<double>&, const GridP<double>&);
+template void launch_con_step<float>(hipStream_t, int, int, const ConP<float>&, const ConStep<float>&, const GridP<float>&, const ThermoArgs*);
+template void launch_con_step<double>(hipStream_t, int, int, const ConP<double>&, const ConStep<double>&, const GridP<double>&, const ThermoArgs*);
 
 }  // namespace mhip

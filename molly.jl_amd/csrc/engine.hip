@@ -58,6 +58,8 @@ struct EngineBase {
     virtual void langevin_run(int64_t, int64_t, double, double, double, int, uint64_t, uint64_t) = 0;
     virtual void redraw_velocities(int, double, double, uint64_t, uint64_t) = 0;
     virtual void set_andersen(double, double, uint64_t) = 0;
+    virtual void set_thermostat(int32_t, double, double, int32_t, int64_t, uint64_t, uint64_t) = 0;
+    virtual void thermostat_info(double*) = 0;
     virtual void vv_stage1(double) = 0;
     virtual void vv_stage2(int64_t, double) = 0;
     virtual void rebuild_now(int64_t) = 0;
@@ -1389,6 +1391,7 @@ template <class T> class Engine final : public EngineBase {
         if (ng > 0 && tri_mode) throw ApiError{MHIP_ERR_UNSUPPORTED, "TriclinicBoundary is single-domain"};
         if (ng > 0 && con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain"};
         if (ng > 0 && vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites run on a single domain"};
+        if (ng > 0 && thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain"};
         n_owned = no; n_ghost = ng; n_tot = no + ng;
         // new local atom set: restart from the identity order
         hipLaunchKernelGGL(k_iota2, dim3(std::min(cdiv(n_tot, 256), 1024)), dim3(256), 0, stream, n_tot, orig[cur].p, inv.p);
@@ -1797,6 +1800,7 @@ template <class T> class Engine final : public EngineBase {
     void vv_stage1(double dt) override {
         if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no constraints: use mhip_vv_run"};
         if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no virtual sites: use mhip_vv_run"};
+        if (thermo_on() && !in_run) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no rescaling thermostat: use mhip_vv_run"};
         if (!frc_valid) throw ApiError{MHIP_ERR_STATE, "vv_stage1 needs forces from vv_init / vv_stage2"};
         lp.cur_dt = dt;
         tr("k_vv1");
@@ -1833,6 +1837,7 @@ template <class T> class Engine final : public EngineBase {
     void vv_stage2(int64_t step_n, double dt) override {
         if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no constraints: use mhip_vv_run"};
         if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no virtual sites: use mhip_vv_run"};
+        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no rescaling thermostat: use mhip_vv_run"};
         stage2_cadenced(step_n, dt, false);
         MHIP_HIP(hipGetLastError());
     }
@@ -1840,6 +1845,7 @@ template <class T> class Engine final : public EngineBase {
     // the same with this rank's Σ m v left as n_parts per-block partials {Px, Py, Pz, M} in cm_parts_dev (no finalize launch): the
     // host all-reduces the whole array and hands it back through remove_cm_parts_dev, where the next first kick re-sums it
     void halo_end_parts(int64_t step_n, double dt, int64_t first, int64_t n, const void* in_dev, double* cm_parts_dev, int32_t n_parts) override {
+        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain, stepped by mhip_vv_run"};
         if (cm_parts_dev && (n_parts < 1 || n_parts > 1024)) throw ApiError{MHIP_ERR_INVALID, "n_parts must be 1..1024"};
         scatter_coords(first, n, in_dev);
         stage2_cadenced(step_n, dt, cm_parts_dev != nullptr, cm_parts_dev, n_parts);
@@ -1923,6 +1929,7 @@ template <class T> class Engine final : public EngineBase {
     DBuf<double> cm_all;         // [0] this rank's {ΣPx, ΣPy, ΣPz, ΣM} of the step before (k_halo_pack), [1 + p] peer p's (k_halo_unpack)
     void set_halo_plan(const mhip_halo_plan* p) override {
         if (!p) { hp_set = false; return; }
+        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain, stepped by mhip_vv_run"};
         if (p->n_recv_rows < 0 || p->n_send_rows < 0 || p->n_cm_peers < 0 || p->n_cm_peers > 26 || p->cm_rows < 0 || p->cm_rows > 4 || p->n_send_cm < 0)
             throw ApiError{MHIP_ERR_INVALID, "halo plan: counts out of range"};
         if ((p->n_recv_rows > 0 && (!p->recv || !p->recv_dst)) || (p->n_send_rows > 0 && (!p->send || !p->send_idx || !p->send_shift)) || (p->n_send_cm > 0 && !p->send_cm_pos))
@@ -1949,6 +1956,7 @@ template <class T> class Engine final : public EngineBase {
     }
     // first kick + drift + pack: after vv_init, after a step that stopped behind its second kick, after a re-plan
     void halo_start(double dt) override {
+        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain, stepped by mhip_vv_run"};
         if (!hp_set) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_plan first"};
         vv_stage1(dt);
         halo_pack(false);
@@ -1959,6 +1967,7 @@ template <class T> class Engine final : public EngineBase {
     void halo_mid(int64_t step_n, double dt, int32_t flags, double* cm_parts_dev, int32_t n_parts) override {
         if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain, stepped by mhip_vv_run / mhip_langevin_run"};
         if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites run on a single domain, stepped by mhip_vv_run / mhip_langevin_run"};
+        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain, stepped by mhip_vv_run"};
         if (!hp_set) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_plan first"};
         const bool cm = (flags & 1) != 0, last = (flags & 2) != 0;
         if (cm && last && (!cm_parts_dev || n_parts < 1 || n_parts > 1024)) throw ApiError{MHIP_ERR_INVALID, "n_parts must be 1..1024"};
@@ -2159,6 +2168,7 @@ template <class T> class Engine final : public EngineBase {
     void domain_run(int64_t first_step, int64_t n_steps, double dt, int32_t remove_cm_every, double* cm_parts_dev, int32_t n_parts, int64_t* steps_done, int32_t* reason, int64_t* counters) override {
         if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain, stepped by mhip_vv_run / mhip_langevin_run"};
         if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites run on a single domain, stepped by mhip_vv_run / mhip_langevin_run"};
+        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain, stepped by mhip_vv_run"};
         if (!hp_set) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_plan first"};
         const bool solo = hp.n_cm_peers == 0 && hp.n_send_rows == 0;
         if (!solo && !xf.routes) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_routes first"};
@@ -2270,6 +2280,7 @@ template <class T> class Engine final : public EngineBase {
         if (!gm) { dom.ready = false; return; }
         if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain"};
         if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites run on a single domain"};
+        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain"};
         if (caller_indexed_topology()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the in-engine re-plan moves atoms between ranks and resets the caller order: contexts with bonded terms, exception lists, special pairs or PME keep the host planner"};
         const int gx = gm->grid[0], gy = gm->grid[1], gz = gm->grid[2];
         if (gx < 1 || gy < 1 || gz < 1 || (int64_t)gx * gy * gz > XFER_MAX_RANKS) throw ApiError{MHIP_ERR_INVALID, "domain geometry: 1 .. 64 bricks"};
@@ -2445,6 +2456,7 @@ template <class T> class Engine final : public EngineBase {
 
     // one MD step of a ghosted sub-domain in two calls around the ghost exchange
     void halo_begin(double dt, const int32_t* idx_dev, const void* shift_dev, int64_t n, void* out_dev) override {
+        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain, stepped by mhip_vv_run"};
         vv_stage1(dt);
         gather_coords(idx_dev, shift_dev, n, out_dev);
     }
@@ -2460,6 +2472,7 @@ template <class T> class Engine final : public EngineBase {
     }
     bool frc_valid_for_split() const { return dual ? inner_valid : !lazy_single; }
     void halo_end(int64_t step_n, double dt, int64_t first, int64_t n, const void* in_dev, double* cm_out4_dev) override {
+        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain, stepped by mhip_vv_run"};
         scatter_coords(first, n, in_dev);
         stage2_cadenced(step_n, dt, cm_out4_dev != nullptr);
         if (cm_out4_dev) {   // this rank's {ΣPx, ΣPy, ΣPz, ΣM} for the all-reduce; nothing pending locally: the TOTAL comes back via remove_cm_dev
@@ -2500,9 +2513,11 @@ template <class T> class Engine final : public EngineBase {
         vv_loop(first_step, n_steps, dt, remove_cm_every, nullptr, 0);
         flush_cm();
         if (items_on()) con_read_back();
+        if (thermo_on()) MHIP_HIP(hipMemcpyAsync(h_thermo, thermo_info_dev.p, 8 * sizeof(double), hipMemcpyDeviceToHost, stream));      // (travels with the closing synchronisation, as the solver's counters do)
         MHIP_HIP(hipGetLastError());
         MHIP_HIP(hipStreamSynchronize(stream));
         if (items_on()) con_after_run();
+        if (thermo_on()) for (int k = 0; k < 8; ++k) thermo_host[k] = h_thermo[k];
     }
     // the step loop of a single domain: forces of first_step are in place.  cm_parts_last (nullable): where the LAST step leaves its Σ m v partials (n_parts_last
     // blocks) instead of registering their removal with the context — mhip_domain_run on one brick, whose caller sums them over the (one) rank.
@@ -2512,7 +2527,8 @@ template <class T> class Engine final : public EngineBase {
     void vv_loop(int64_t first_step, int64_t n_steps, double dt, int remove_cm_every, double* cm_parts_last, int n_parts_last) {
         const int every = rebuild_every();
         // fused stepping: first kick + drift once, then ONE integrator launch between consecutive force passes (k_vv_mid), the
-        // plain second kick at the end.  A thermostat needs v_n between the kicks: the two-launch form then (never with constraints: set_andersen refuses them).
+        // plain second kick at the end.  The Andersen thermostat needs v_n between the kicks: the two-launch form then (never with constraints: set_andersen refuses them).
+        // A rescaling thermostat (thermostat.h) keeps the fused form; on the steps where it applies the integrator stage is a close and an open launch (thermo_step).
         const bool fused = !(andersen_prob > 0);
         InRun guard_fused(in_vv_fused); in_vv_fused = fused;
         const bool pre = dual;                                                    // without the dual list: the reference's order
@@ -2534,6 +2550,7 @@ template <class T> class Engine final : public EngineBase {
             if (trk_issued && step > trk_step) resolve_track(step);
             if (pre && lp.check_due(step, every)) refresh(step);
             const bool cm = remove_cm_every != 0 && step % remove_cm_every == 0;
+            const bool th = thermo_on() && step % thermo.n_steps == 0;            // :630, behind this step's CM removal
             if (!fused) {
                 stage2_impl(step, dt, cm);                                        // :612-628
                 apply_coupling(step);                                             // :630
@@ -2542,7 +2559,7 @@ template <class T> class Engine final : public EngineBase {
             }
             // the validity check of step + 1 is measured where its coordinates are made: by this step's integrator launch — or by the pair pass itself when it integrates
             const bool measure = step != last && async_ok() && !trk_issued && lp.check_due(step + 1, every);
-            const bool integrate = step != last && !items_on();
+            const bool integrate = step != last && !items_on() && !th;            // (λ needs Σ m v² of ALL atoms between the kicks: no force launch integrates on such a step)
             PassReq req;
             req.step = integrate && !bonded.any() && !pme.on(); req.cm = cm;      // (one kernel either way: its stage time is its own, so the stage timers leave it fused)
             req.gcv = integrate && bonded.any() && pme.on() && (pre || !lp.check_due(step, every));      // (a re-sort behind the pass would want the total force array)
@@ -2563,15 +2580,65 @@ template <class T> class Engine final : public EngineBase {
             // the speeds for a check that the next step's force pass will measure (see resolve_track); evaluated behind the pass: a prune inside it makes the lists checkable again
             const bool measure_mid = step != last && async_ok() && !trk_issued && lp.check_due(step + 1, every);
             if (measure_mid) trk_reserve(n_blocks);
-            if (items_on()) con_launch(step == last ? 2 : 1, nb, dt, cm_out, measure_mid, nullptr);
+            if (th) thermo_step(step, step == last, nb, dt, cm_out, measure_mid);
+            else if (items_on()) con_launch(step == last ? 2 : 1, nb, dt, cm_out, measure_mid, nullptr);
             else vv_mid_launch(cm, step == last, nb, dt, pending_cm.parts_arg(), pending_cm.n, cm_out, measure_mid);
             prof.end(2, stream);
             if (measure_mid) issue_track(nb, step + 1);   // the check of step + 1, read by resolve_track at step + 2
             if (step == last) frc_run_total = pend_a == nullptr && n_ghost == 0;   // (side arrays are added by the kick, not folded)
             pend_a = nullptr; pending_cm.none();
-            if (cm && !parts_out) { pending_cm.resum(cm_out, nb); half ^= 1; }
+            if (cm && !parts_out && !th) { pending_cm.resum(cm_out, nb); half ^= 1; }      // (th: removed with the scale, nothing is pending)
             if (step != last) frc_valid = false;                                  // frc[cur] belongs to the coordinates before the drift
         }
+    }
+
+    // ---- rescaling thermostats (thermostat.h, thermostat_step.h): Immediate, Berendsen, VelocityRescale as the coupling of mhip_vv_run ---------
+    ThermoP thermo; DBuf<double> thermo_part, thermo_info_dev; Pinned<double> h_thermo; double thermo_host[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool thermo_on() const { return thermo.kind != THERMO_OFF; }
+    void set_thermostat(int32_t kind, double kT, double tau, int32_t n_steps, int64_t dof, uint64_t key, uint64_t ctr1) override {
+        if (kind < THERMO_OFF || kind > THERMO_CSVR) throw ApiError{MHIP_ERR_INVALID, "thermostat kind must be 0 (off), 1 (Immediate), 2 (Berendsen) or 3 (VelocityRescale)"};
+        if (kind != THERMO_OFF) {
+            if (!(kT > 0) || !(tau > 0) || n_steps < 1) throw ApiError{MHIP_ERR_INVALID, "thermostat: kT, coupling_const and n_steps must be positive"};
+            if (kind != THERMO_CSVR && n_steps != 1) throw ApiError{MHIP_ERR_INVALID, "thermostat: ImmediateThermostat and BerendsenThermostat apply every step (n_steps = 1)"};
+            if (andersen_prob > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "a rescaling thermostat next to the Andersen coupling is not supported"};
+            if (n_ghost > 0 || dom.ready || hp_set || xf.world > 1) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain"};
+        }
+        thermo = ThermoP{};
+        if (kind == THERMO_OFF) return;      // the context steps as one that never had a thermostat (the record of the last one stays readable)
+        thermo_info_dev.reserve(8); h_thermo.make(8); thermo_part.reserve(2 * 1024);      // (one partial per block of the close launch: at most 1024, as cm_step's halves)
+        MHIP_HIP(hipMemsetAsync(thermo_info_dev.p, 0, 8 * sizeof(double), stream));
+        for (double& x : thermo_host) x = 0;
+        thermo.kind = kind; thermo.n_steps = n_steps; thermo.dof = dof; thermo.kT = kT; thermo.tau = tau; thermo.key = key; thermo.ctr1 = ctr1;
+    }
+    void thermostat_info(double* out8) override { for (int k = 0; k < 8; ++k) out8[k] = thermo_host[k]; }
+    // the integrator stage of a step on which the thermostat applies: the close launch (closing kick, RATTLE, Σ m v and the thermostat partials), then the open
+    // launch (λ from the partials, v = λ·(v − v_cm), first kick, drift, SHAKE, the check of step + 1) — or, on the run's last step, the flush of the scale
+    void thermo_step(int64_t step, bool last, int nb, double dt, double* cm_out, bool measure) {
+        ThermoP P = thermo;
+        P.step = step; P.ctr1 = thermo.ctr1 + (uint64_t)step; P.dt = dt; P.natoms = (uint64_t)cfg.n_atoms; P.info = thermo_info_dev.p;
+        if (items_on()) con_launch(2, nb, dt, cm_out, false, nullptr, &P, nullptr, thermo_part.p);
+        else {
+            tr("k_vv_close");
+            auto go = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, stream, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, T(dt), T(dt) / T(2), pending_cm.parts_arg(), pending_cm.n, cm_out,
+                                   (const T4*)pend_a, G, P, thermo_part.p);
+            };
+            if (cm_out) go(k_vv_close<T, true>); else go(k_vv_close<T, false>);      // (wrote the total force back into frc[cur])
+        }
+        pending_cm.none();                       // consumed by the close launch; this step's removal goes with the scale
+        if (last) {                              // (the flush is timed as a stage-2 call of its own; close + open are ONE integrator stage, as k_vv_mid is)
+            prof.end(2, stream);
+            prof.begin(2, stream);
+            tr("k_scale_vel");
+            hipLaunchKernelGGL(k_scale_vel<T>, dim3(std::min(cdiv(n_owned, 256), 1024)), dim3(256), 0, stream, n_owned, vel[cur].p, (const double*)cm_out, (const double*)thermo_part.p, nb, P,
+                               vs_on ? (const int32_t*)orig[cur].p : nullptr, (const uint8_t*)vs_flag.p);
+        } else if (items_on()) con_launch(0, nb, dt, nullptr, measure, nullptr, &P, thermo_part.p, nullptr, cm_out);
+        else {
+            tr("k_vv_open");
+            hipLaunchKernelGGL(k_vv_open<T>, dim3(nb), dim3(256), 0, stream, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, T(dt), T(dt) / T(2), (const double*)cm_out, (const double*)thermo_part.p, nb, P, G,
+                               measure ? (const T4*)pos_snap_in.p : (const T4*)nullptr, measure ? (const T4*)pos_snap.p : (const T4*)nullptr, measure ? trk_part.p : (float*)nullptr);
+        }
+        MHIP_HIP(hipGetLastError());
     }
 
     // ---- SHAKE_RATTLE (constraints.h): clusters built on the host, one lane per cluster between consecutive force passes -----------------
@@ -2711,7 +2778,8 @@ template <class T> class Engine final : public EngineBase {
     void con_read_back() { MHIP_HIP(hipMemcpyAsync(h_con, con_stat.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream)); }
     void con_after_run() { con_fails = (int64_t)h_con[0]; con_last_max = (int64_t)h_con[1]; }
     // one k_con_step launch (mode: constraints.h) over the current order, the pending Σ m v removal in front
-    void con_launch(int mode, int nb, double dt, double* cm_out, bool measure, const StochP<T>* S) {
+    // th (nullable): a coupled step's close (mode 2, th_out) or open launch (mode 0; th_in and th_cm_in — nullable — are the close launch's nb partials)
+    void con_launch(int mode, int nb, double dt, double* cm_out, bool measure, const StochP<T>* S, const ThermoP* th = nullptr, const double* th_in = nullptr, double* th_out = nullptr, const double* th_cm_in = nullptr) {
         ConP<T> C{};
         C.atoms = con_atoms.p; C.d = con_d.p; C.inv = inv.p; for (int k = 0; k < CK_N; ++k) C.end[k] = con.end[k];
         C.tol = con_tol; C.max_iters = con_iters; C.stat = con_stat.p;
@@ -2722,8 +2790,10 @@ template <class T> class Engine final : public EngineBase {
         A.snap_a = measure ? (const T4*)pos_snap_in.p : nullptr; A.snap_b = measure ? (const T4*)pos_snap.p : nullptr; A.trk_part = measure ? trk_part.p : nullptr;
         A.dt = T(dt); A.dt2 = T(dt) / T(2);
         if (S) A.S = *S;
+        ThermoArgs X;
+        if (th) { X.th = *th; X.th_in = th_in; X.th_out = th_out; if (th_in) { A.vcm = nullptr; A.cm_in = th_cm_in; A.n_cm_in = nb; } }
         tr("k_con_step");
-        launch_con_step<T>(stream, nb, mode, C, A, G);
+        launch_con_step<T>(stream, nb, mode, C, A, G, th ? &X : nullptr);
         MHIP_HIP(hipGetLastError());
     }
     // ---- stochastic dynamics (kernels in stochastic.hip) ------------------------------------------------------
@@ -2751,6 +2821,7 @@ template <class T> class Engine final : public EngineBase {
     void set_andersen(double kT, double prob, uint64_t seed) override {
         if (prob > 0 && con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen thermostat with constraints is not supported (a re-drawn velocity breaks RATTLE)"};
         if (prob > 0 && vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen thermostat with virtual sites is not supported"};
+        if (prob > 0 && thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen coupling next to a rescaling thermostat is not supported"};
         andersen_kT = kT; andersen_prob = prob; andersen_seed = seed;
     }
     void apply_coupling(int64_t step) {
@@ -2765,6 +2836,7 @@ template <class T> class Engine final : public EngineBase {
     void langevin_run(int64_t first_step, int64_t n_steps, double dt, double kT, double friction, int remove_cm_every, uint64_t key, uint64_t ctr1_0) override {
         if (!state_set || !params_set) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before langevin_run"};
         if (n_ghost > 0) throw ApiError{MHIP_ERR_STATE, "langevin_run is single-domain"};
+        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats are a coupling of mhip_vv_run: unset the thermostat before mhip_langevin_run"};
         if (!(kT >= 0) || !(friction >= 0)) throw ApiError{MHIP_ERR_INVALID, "temperature and friction must be non-negative"};
         const int every = rebuild_every();
         lp.cur_dt = dt;
@@ -3040,6 +3112,10 @@ int32_t mhip_langevin_run(mhip_ctx* ctx, int64_t first, int64_t n, double dt, do
 int32_t mhip_random_velocities(mhip_ctx* ctx, double kT, uint64_t key, uint64_t ctr1) { NEED_CTX(); return guard(ctx, [&] { ctx->e->redraw_velocities(1, kT, 1.0, key, ctr1); }); }
 int32_t mhip_andersen(mhip_ctx* ctx, double kT, double prob, uint64_t key, uint64_t ctr1) { NEED_CTX(); return guard(ctx, [&] { ctx->e->redraw_velocities(0, kT, prob, key, ctr1); }); }
 int32_t mhip_set_andersen(mhip_ctx* ctx, double kT, double prob, uint64_t seed) { NEED_CTX(); return guard(ctx, [&] { ctx->e->set_andersen(kT, prob, seed); }); }
+int32_t mhip_set_thermostat(mhip_ctx* ctx, int32_t kind, double kT, double coupling_const, int32_t n_steps, int64_t dof, uint64_t key, uint64_t ctr1) {
+    NEED_CTX(); return guard(ctx, [&] { ctx->e->set_thermostat(kind, kT, coupling_const, n_steps, dof, key, ctr1); });
+}
+int32_t mhip_thermostat_info(mhip_ctx* ctx, double* out8) { NEED_CTX(); return guard(ctx, [&] { if (!out8) throw mhip::ApiError{MHIP_ERR_INVALID, "null output"}; ctx->e->thermostat_info(out8); }); }
 int32_t mhip_philox4x32_10(const uint32_t* ctr4, const uint32_t* key2, uint32_t* out4) {
     if (!ctr4 || !key2 || !out4) return MHIP_ERR_INVALID;
     const uint32_t h[6] = {ctr4[0], ctr4[1], ctr4[2], ctr4[3], key2[0], key2[1]};

@@ -15,6 +15,7 @@
 #include "physics.h"
 #include "halo_xfer.h"
 #include "philox.h"
+#include "thermostat_step.h"
 
 namespace mhip {
 
@@ -2163,11 +2164,16 @@ __global__ void k_vv2(int64_t n, typename Vec<T>::T4* vel, typename Vec<T>::T4* 
 // removal), carries on with the unshifted velocity, and the NEXT launch subtracts v_cm from the velocity it finds and v_cm·dt from
 // the position that was drifted with it.  The forces in between saw every atom translated by the same v_cm·dt (≈ 1e-11 nm): they are
 // translation invariant.  LAST: stop after the second kick (the run's final step), leaving v_n and x_n for the caller.
-template <class T, bool CM, bool LAST>
-__global__ void k_vv_mid(int64_t n, typename Vec<T>::T4* pos, typename Vec<T>::T4* vel, const typename Vec<T>::T4* __restrict__ fr, T dt, T dt2,
-                         const double* __restrict__ cm_in, int n_cm_in, double* cm_out,
-                         const typename Vec<T>::T4* __restrict__ fa, GridP<T> G,
-                         const typename Vec<T>::T4* __restrict__ snap_a = nullptr, const typename Vec<T>::T4* __restrict__ snap_b = nullptr, float* trk_part = nullptr) {
+// TH (with LAST: the close launch of a step on which a rescaling thermostat applies, thermostat_step.h): one more per-block output, th_out =
+// {Σ m|v|² of the velocities as stored, this block's share of the CSVR noise}.  The body is shared by two kernels: k_vv_mid, whose arguments and code
+// are what they were, and k_vv_close, which carries the thermostat's.
+template <class T, bool CM, bool LAST, bool TH>
+__device__ __forceinline__ void vv_mid_body(int64_t n, typename Vec<T>::T4* pos, typename Vec<T>::T4* vel, const typename Vec<T>::T4* __restrict__ fr, T dt, T dt2,
+                                            const double* __restrict__ cm_in, int n_cm_in, double* cm_out,
+                                            const typename Vec<T>::T4* __restrict__ fa, const GridP<T>& G,
+                                            const typename Vec<T>::T4* __restrict__ snap_a, const typename Vec<T>::T4* __restrict__ snap_b, float* trk_part,
+                                            const ThermoP& th, double* th_out) {
+    static_assert(!TH || LAST, "the thermostat's partials are taken by a launch that stops after the closing kick");
     const typename Vec<T>::T4* __restrict__ frc = fr;
     // trk_part (the validity check of the pair lists, taken where the new coordinates are made): per block the largest |x − snap_a|²,
     // |x − snap_b|² and |v|² of what this launch leaves behind, trk_part[c·gridDim.x + block]
@@ -2189,6 +2195,7 @@ __global__ void k_vv_mid(int64_t n, typename Vec<T>::T4* pos, typename Vec<T>::T
     if (sub) block_vcm<T>(cm_in, n_cm_in, vc);
     const T sh[3] = {M<T>::mul(vc[0], dt), M<T>::mul(vc[1], dt), M<T>::mul(vc[2], dt)};
     double px = 0, py = 0, pz = 0, m = 0;
+    [[maybe_unused]] double mv2 = 0;
     for (; s < n; s = sn) {
         sn = s + stride;
         const auto v0 = vq, f0 = fq, p0 = pq, ga0 = gaq;
@@ -2202,6 +2209,7 @@ __global__ void k_vv_mid(int64_t n, typename Vec<T>::T4* pos, typename Vec<T>::T
         const T kx = M<T>::mul(accel_of(f.x, v.w), dt2), ky = M<T>::mul(accel_of(f.y, v.w), dt2), kz = M<T>::mul(accel_of(f.z, v.w), dt2);
         v.x = M<T>::add(v.x, kx); v.y = M<T>::add(v.y, ky); v.z = M<T>::add(v.z, kz);   // :616, v_n before this step's CM removal
         if constexpr (CM) { px += (double)v.x * v.w; py += (double)v.y * v.w; pz += (double)v.z * v.w; m += v.w; }
+        if constexpr (TH) thermo_accum<T>(v, mv2);
         if constexpr (!LAST) {
             v.x = M<T>::add(v.x, kx); v.y = M<T>::add(v.y, ky); v.z = M<T>::add(v.z, kz);   // :594 of the next step
             p.x = step_add(p.x, v.x, dt); p.y = step_add(p.y, v.y, dt); p.z = step_add(p.z, v.z, dt);   // :602
@@ -2239,6 +2247,59 @@ __global__ void k_vv_mid(int64_t n, typename Vec<T>::T4* pos, typename Vec<T>::T
         if ((threadIdx.x & 63) == 0) { shm[w][0] = px; shm[w][1] = py; shm[w][2] = pz; shm[w][3] = m; }
         __syncthreads();
         if (threadIdx.x < 4) { double a = 0; for (int q = 0; q < (int)(blockDim.x >> 6); ++q) a += shm[q][threadIdx.x]; cm_out[4 * (int64_t)blockIdx.x + threadIdx.x] = a; }
+    }
+    if constexpr (TH) thermo_write_partial(mv2, thermo_noise_share<T>(th), th_out);
+}
+template <class T, bool CM, bool LAST>
+__global__ void k_vv_mid(int64_t n, typename Vec<T>::T4* pos, typename Vec<T>::T4* vel, const typename Vec<T>::T4* __restrict__ fr, T dt, T dt2,
+                         const double* __restrict__ cm_in, int n_cm_in, double* cm_out,
+                         const typename Vec<T>::T4* __restrict__ fa, GridP<T> G,
+                         const typename Vec<T>::T4* __restrict__ snap_a = nullptr, const typename Vec<T>::T4* __restrict__ snap_b = nullptr, float* trk_part = nullptr) {
+    vv_mid_body<T, CM, LAST, false>(n, pos, vel, fr, dt, dt2, cm_in, n_cm_in, cm_out, fa, G, snap_a, snap_b, trk_part, ThermoP{}, nullptr);
+}
+// the close launch of a coupled step: k_vv_mid<…, LAST> with the thermostat partials as one more output
+template <class T, bool CM>
+__global__ void k_vv_close(int64_t n, typename Vec<T>::T4* pos, typename Vec<T>::T4* vel, const typename Vec<T>::T4* __restrict__ fr, T dt, T dt2,
+                           const double* __restrict__ cm_in, int n_cm_in, double* cm_out,
+                           const typename Vec<T>::T4* __restrict__ fa, GridP<T> G, ThermoP th, double* th_out) {
+    vv_mid_body<T, CM, true, true>(n, pos, vel, fr, dt, dt2, cm_in, n_cm_in, cm_out, fa, G, nullptr, nullptr, nullptr, th, th_out);
+}
+
+// the scale, then the first kick + drift + wrap of the next step (k_vv1's arithmetic) and the maxima of the pair lists' validity check
+// as k_vv_mid measures them.  No position shift: the drift happens after the removal.
+template <class T>
+__global__ void __launch_bounds__(256) k_vv_open(int64_t n, typename Vec<T>::T4* pos, typename Vec<T>::T4* vel, const typename Vec<T>::T4* __restrict__ frc, T dt, T dt2,
+                                                 const double* __restrict__ cm_part, const double* __restrict__ th_part, int n_part, ThermoP P, GridP<T> G,
+                                                 const typename Vec<T>::T4* __restrict__ snap_a, const typename Vec<T>::T4* __restrict__ snap_b, float* trk_part) {
+    T vc[3];
+    const T lam = thermo_block_lambda<T>(cm_part, th_part, n_part, P, vc);
+    const bool sub = cm_part != nullptr;
+    float v2m = 0.f, dam = 0.f, dbm = 0.f;
+    for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
+        auto v = vel[s]; auto p = pos[s]; const auto f = frc[s];
+        thermo_scale<T>(v, vc, sub, lam);
+        v.x = step_add(v.x, accel_of(f.x, v.w), dt2); v.y = step_add(v.y, accel_of(f.y, v.w), dt2); v.z = step_add(v.z, accel_of(f.z, v.w), dt2);   // :594
+        p.x = step_add(p.x, v.x, dt); p.y = step_add(p.y, v.y, dt); p.z = step_add(p.z, v.z, dt);   // :602
+        wrap_point(p.x, p.y, p.z, G);                                          // :609
+        vel[s] = v; pos[s] = p;
+        if (trk_part) {
+            v2m = fmaxf(v2m, (float)(v.x * v.x + v.y * v.y + v.z * v.z));
+            auto q = snap_a[s];
+            T ex = p.x - q.x, ey = p.y - q.y, ez = p.z - q.z;
+            disp_image(ex, ey, ez, G);
+            dam = fmaxf(dam, (float)(ex * ex + ey * ey + ez * ez));
+            q = snap_b[s];
+            ex = p.x - q.x; ey = p.y - q.y; ez = p.z - q.z;
+            disp_image(ex, ey, ez, G);
+            dbm = fmaxf(dbm, (float)(ex * ex + ey * ey + ez * ez));
+        }
+    }
+    if (trk_part) {
+        __shared__ float sht[3][16];
+        dam = wave_max(dam); dbm = wave_max(dbm); v2m = wave_max(v2m);
+        if ((threadIdx.x & 63) == 0) { sht[0][threadIdx.x >> 6] = dam; sht[1][threadIdx.x >> 6] = dbm; sht[2][threadIdx.x >> 6] = v2m; }
+        __syncthreads();
+        if (threadIdx.x < 3) { float m = 0.f; for (int q = 0; q < (int)(blockDim.x >> 6); ++q) m = fmaxf(m, sht[threadIdx.x][q]); trk_part[threadIdx.x * gridDim.x + blockIdx.x] = m; }
     }
 }
 
@@ -2300,6 +2361,21 @@ __global__ void k_shift_vel(int64_t n, typename Vec<T>::T4* vel, const T* __rest
     for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
         if (orig && skip[orig[s]]) continue;
         auto v = vel[s]; v.x -= vc[0]; v.y -= vc[1]; v.z -= vc[2]; vel[s] = v;
+    }
+}
+
+// the flush of a scale that the run's last step left pending (k_shift_vel's sibling); skip as there: a virtual site's velocity is left alone
+template <class T>
+__global__ void __launch_bounds__(256) k_scale_vel(int64_t n, typename Vec<T>::T4* vel, const double* __restrict__ cm_part, const double* __restrict__ th_part, int n_part, ThermoP P,
+                                                   const int32_t* __restrict__ orig, const uint8_t* __restrict__ skip) {
+    T vc[3];
+    const T lam = thermo_block_lambda<T>(cm_part, th_part, n_part, P, vc);
+    const bool sub = cm_part != nullptr;
+    for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
+        if (orig && skip[orig[s]]) continue;
+        auto v = vel[s];
+        thermo_scale<T>(v, vc, sub, lam);
+        vel[s] = v;
     }
 }
 
