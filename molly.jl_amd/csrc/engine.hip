@@ -259,7 +259,7 @@ template <class T> class Engine final : public EngineBase {
     bool coords_moved = false, export_needs_search = false; int64_t n_set_state_refresh = 0;
     int64_t last_build_step = std::numeric_limits<int64_t>::min();
     int64_t n_rebuilds = 0, n_force_calls = 0, n_gs_passes = 0; double last_rebuild_ms = 0;
-    size_t lds_force = 0; int tile_lds = 0; bool segmented = false; int last_pass_tile = 0;
+    PassPlan last_plan;      // what the last block pass launched with (pass_plan.h); a group-split pass, which stages no such tile, leaves only its tile_max
     Prof prof;
     // MOLLYHIP_DEBUG=2: drain the stream, then name the launch that follows on stderr — the last name a dying process printed is the
     // kernel that faulted (a GPU fault aborts the process from the runtime's callback, no status ever comes back)
@@ -422,12 +422,6 @@ template <class T> class Engine final : public EngineBase {
         // tile (coords + slot) | max(cell tables, per-wave candidate bit masks) | scan scratch
         // tile (coords + caller index) | cell tables | scan scratch | per-lane exception lists
         return (size_t)tcap * (3 * sizeof(float) + (has_exc ? 4 : 0)) + (2 * (size_t)ccap + 2) * 4 + 8 + (size_t)bi * JS * 4 + (has_exc ? (size_t)X_CAP * bi * 4 : 0) + (walk ? ((size_t)ccap + 2) * 4 : 0) + 64;   // … | first tile slot per box cell (walk)
-    }
-    size_t force_lds_bytes(int tlds) const {
-        const bool per_atom_lj = (ljm == LJ_DIST || ljm == LJ_GENERIC);
-        size_t tile = (size_t)(tlds + 1) * (sizeof(T4) + (per_atom_lj ? sizeof(T2) : 0));
-        size_t red = (size_t)JS * 4 * BI * sizeof(T);
-        return std::max(std::max(tile, red), (size_t)BI * sizeof(double)) + 32;
     }
 
     void choose_blocking() {
@@ -655,7 +649,8 @@ template <class T> class Engine final : public EngineBase {
         }
         minimg = h_flags[FLAG_MINIMG] != 0;
         max_tile = h_flags[FLAG_MAX_TILE]; max_rows = h_flags[FLAG_MAX_ROWS]; total_rows = outer_rows = h_flags[FLAG_TOTAL_ROWS];
-        carve_force_lds(max_tile);
+        last_plan = PassPlan{}; plan_tile(last_plan, pass_shape(false, 0, false, PassReq{}), max_tile);      // (mhip_get_stats before the first pass over the new list)
+        throw_capacity(last_plan);
         red_part.reserve(std::max<size_t>(7 * (size_t)n_blocks, 4 * (size_t)cdiv(n_owned, 256)) + 8);
         bonded.on_reorder();
         ++n_outer; lp.last_outer_step = step_n;
@@ -680,20 +675,6 @@ template <class T> class Engine final : public EngineBase {
         last_rebuild_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
 
-    // LDS carve-up of the force kernel: the whole tile if it fits the budget, else segments of the budget's size
-    void carve_force_lds(int tile_max, size_t reserve = 0) {   // reserve: bytes the caller places behind the carve-up (prune pass: marks + scan scratch)
-        size_t budget = std::min<size_t>((size_t)env_int("MOLLYHIP_LDS_BUDGET_KB", 160) * 1024, MAX_LDS_BYTES);
-        if (budget > reserve + 8192) budget -= reserve;
-        const bool per_atom_lj = (ljm == LJ_DIST || ljm == LJ_GENERIC);
-        const size_t per_atom = sizeof(T4) + (per_atom_lj ? sizeof(T2) : 0);
-        const size_t fixed = std::max((size_t)JS * 4 * BI * sizeof(T), (size_t)BI * sizeof(double)) + 64;
-        int fit = (int)((budget > fixed + 2 * per_atom ? budget - fixed : 2 * per_atom) / per_atom) - 1;
-        fit = std::max(fit & ~1, 2);
-        segmented = tile_max > fit;
-        tile_lds = segmented ? fit : std::max(tile_max, 1);
-        lds_force = force_lds_bytes(tile_lds);
-        if (lds_force > (size_t)MAX_LDS_BYTES) throw ApiError{MHIP_ERR_CAPACITY, "force-kernel LDS carve-up exceeds 160 KiB"};
-    }
 
     // the exact list of radius r_list at the current coordinates for mhip_export_neighbors: the outer list filtered with the reference's predicate into its
     // OWN arrays (nbr_x, tile_idx_x: the inner list of the force passes keeps referring to tile_idx_in), + max displacement since the outer build.
@@ -863,18 +844,13 @@ template <class T> class Engine final : public EngineBase {
 
     // ---------------------------------------------------------------------------------------------
     // the pair-kernel variants are compiled in forces_inst.hip (one translation unit per precision and Coulomb kind)
-    void launch_forces_any(const ForceArgs<T>& A, bool energy) {
-        const bool prune = A.nbr_dst != nullptr && !energy;
-        const unsigned threads = (unsigned)(BI * JS);
-        if (lds_force > (size_t)MAX_LDS_BYTES) throw ApiError{MHIP_ERR_CAPACITY, "atom tile does not fit the 160 KiB LDS"};
+    void launch_forces_any(const ForceArgs<T>& A, const PassPlan& plan, bool energy) {
+        auto go = [&](auto kind) { launch_forces_tc<T, decltype(kind)::value>(A, ljm, energy, minimg, plan.segmented, plan.prune, plan.lds_bytes, (unsigned)(BI * JS), stream); };
         switch (coulm) {
-        case MHIP_COUL_NONE: launch_forces_tc<T, MHIP_COUL_NONE>(A, ljm, energy, minimg, segmented, prune, lds_force, threads, stream); break;
-        case MHIP_COUL_PLAIN: launch_forces_tc<T, MHIP_COUL_PLAIN>(A, ljm, energy, minimg, segmented, prune, lds_force, threads, stream); break;
-        case MHIP_COUL_REACTION_FIELD: launch_forces_tc<T, MHIP_COUL_REACTION_FIELD>(A, ljm, energy, minimg, segmented, prune, lds_force, threads, stream); break;
-        default:
-            if (I.approx_erfc) launch_forces_tc<T, MHIP_COUL_EWALD_DIRECT>(A, ljm, energy, minimg, segmented, prune, lds_force, threads, stream);
-            else launch_forces_tc<T, COUL_EWALD_EXACT>(A, ljm, energy, minimg, segmented, prune, lds_force, threads, stream);
-            break;
+        case MHIP_COUL_NONE: go(std::integral_constant<int, MHIP_COUL_NONE>{}); break;
+        case MHIP_COUL_PLAIN: go(std::integral_constant<int, MHIP_COUL_PLAIN>{}); break;
+        case MHIP_COUL_REACTION_FIELD: go(std::integral_constant<int, MHIP_COUL_REACTION_FIELD>{}); break;
+        default: if (I.approx_erfc) go(std::integral_constant<int, MHIP_COUL_EWALD_DIRECT>{}); else go(std::integral_constant<int, COUL_EWALD_EXACT>{}); break;
         }
     }
     // What one force pass (step_forces, launch_pair_kernel) is asked to do beyond the forces; the default is a plain pass.
@@ -897,89 +873,110 @@ template <class T> class Engine final : public EngineBase {
         bool gs = false, spread = false, terms = false;      // a group-split pass | with the charge spreading | with the bonded terms
         bool cm_summed = false;                 // req.cm_sum_in summed into cm_fin_buf
     };
-    // The packed fp32 one-type loop keeps the tile as three arrays SOA_STRIDE dwords apart.  packed_kind: the passes it can run;
-    // packed_stride: the smallest stride that holds a tile of tile_max atoms + sentinel, 0 for any other loop (segmented as carve_force_lds(tile_max) left it).
-    // The one answer launch_pair_kernel and packed_step_possible go by.
-    bool packed_kind(bool energy) const {
-        return std::is_same<T, float>::value && ljm == LJ_DIST_UNIFORM && coulm == MHIP_COUL_NONE && !energy && !minimg && n_special == 0 && eshift == ESHIFT_SCALED && I.lj_c12 != T(0);
+    // The pair pass in four steps: plan (pass_plan.h: which form, which list, what LDS — host arithmetic on the PassShape below), fill the arguments the form
+    // reads, launch, and what a pruning pass leaves to do afterwards.
+    PassShape pass_shape(bool energy, int part, bool allow_gs, const PassReq& req) {
+        PassShape s;
+        s.fp32 = std::is_same<T, float>::value; s.ljm = ljm; s.coulm = coulm; s.minimg = minimg; s.n_special = n_special > 0 ? 1 : 0; s.eshift = eshift; s.lj_c12 = I.lj_c12 != T(0);
+        s.BI = BI; s.JS = JS; s.T_cap = T_cap; s.lds_budget = (size_t)env_int("MOLLYHIP_LDS_BUDGET_KB", 160) * 1024;
+        s.dual = dual; s.inner_valid = inner_valid; s.max_tile = max_tile; s.max_tile_in = max_tile_in;
+        s.gs = gs_groups(); s.gs_list_current = gs_list_id == n_filters; s.n_ghost = n_ghost;
+        s.energy = energy; s.part = part; s.allow_gs = allow_gs; s.own_frc = req.frc != nullptr;
+        s.step = req.step; s.halo = req.halo; s.fuse_step = fuse_step_env;
+        s.cm_mode = pending_cm.mode(); s.cm_n = pending_cm.n; s.in_step_loop = in_vv_fused || in_lang_fused;
+        return s;
     }
-    int packed_stride(int tile_max, bool energy) const {
-        if (!packed_kind(energy) || segmented) return 0;
-        for (int k = 0; k < 3; ++k) if (tile_max + 1 < SOA_STRIDES[k]) return SOA_STRIDES[k];
-        return 0;
-    }
+    static void throw_capacity(const PassPlan& plan) { if (plan.capacity != PassCapacity::OK) throw ApiError{MHIP_ERR_CAPACITY, capacity_message(plan.capacity)}; }
+
     // pairwise forces of the current coordinates into frc[cur] (overwrites); energy → red_part[0..n_blocks)
     PassRes launch_pair_kernel(bool energy, int part = 0, bool allow_gs = false, const PassReq& req = PassReq{}) {
-        PassRes res;
         prune_resolve(!(xf_direct && n_ghost > 0));      // figures a pruning pass left behind an event: taken if they have arrived (outside the ghosted run loop: waited for)
-        ForceArgs<T> A;
-        A.G = G; A.I = I; A.n_owned = n_owned; A.BI = BI; A.BI_shift = ilog2(BI); A.JS = JS; A.T_cap = T_cap; A.T_lds = tile_lds; A.R_cap = R_cap;
-        A.n_blocks = n_blocks; A.blocks_per_xcd = cdiv(n_blocks, 8);
-        A.orig = nullptr; A.S = StochP<T>{};      // (LANG variants only)
-        A.pos = pos[cur].p; A.lj = lj[cur].p; A.tile_idx = tile_idx.p; A.tile_cnt = tile_cnt.p;
-        // dual pair list: a force pass whose inner list is stale walks the OUTER list (always a valid superset — the cutoff is
-        // applied per pair) and, if it is a plain force call, prunes it into the inner list on the way
+        // dual pair list: a force pass whose inner list is stale walks the OUTER list (always a valid superset — the cutoff is applied per pair) and, if it is a
+        // plain force call, prunes it into the inner list on the way — unless the outer list, searched at this very step with the prune radius, can be adopted as it is
         if constexpr (std::is_same<T, float>::value) {
             if (dual && !inner_valid && !energy && allow_gs && part == 0 && !req.frc && adopt_env && gs_groups() > 0 && cnt_outer_valid && margin_zero && !(lp.skin_in < lp.skin)
                 && lp.last_outer_step == pass_step && n_ghost == 0 && !host_prune) adopt_outer_list();
         }
-        const bool use_inner = dual && inner_valid;
-        const bool prune = dual && !inner_valid && !energy;
-        const int GS = gs_groups();
-        // a plain pass over an inner list that has its group-split form (made right behind the prune that wrote it)
-        if constexpr (std::is_same<T, float>::value) {
-            if (allow_gs && GS > 0 && use_inner && !energy && part == 0 && gs_list_id == n_filters && !req.frc) {
-                const int q_lds = (max_tile_in + GS - 1) / GS + 1;      // (max_tile_in = max_tile while the outer list stands in)
-                if (gs_lds_bytes(q_lds, BI, JS / GS) <= (size_t)MAX_LDS_BYTES / GS) {
-                    frc_parts.reserve((size_t)(GS - 1) * cap);
-                    GsArgs Z;
-                    Z.G = G; Z.I = I; Z.n_owned = n_owned; Z.BI = BI; Z.BI_shift = ilog2(BI); Z.JS = JS; Z.GS = GS; Z.lgGS = ilog2(GS); Z.R_cap = GS * R_cap;      // (the group-split list's own row capacity: RegroupArgs::R_cap_dst)
-                     Z.T_cap = T_cap; Z.Q_lds = q_lds;
-                    Z.n_blocks = n_blocks; Z.spread = std::max(1, n_blocks / GS + 5);
-                    Z.pos = pos[cur].p; Z.lj = lj[cur].p; Z.tile_idx = inner_is_outer ? tile_idx.p : tile_idx_in.p; Z.tile_cnt = inner_is_outer ? tile_cnt.p : tile_cnt_in.p; Z.nbr = nbr_gs.p; Z.wave_rows = rows_gs.p; Z.blk_center = blk_center.p;
-                    Z.frc = frc[cur].p; Z.parts = frc_parts.p; Z.part_stride = cap;
-                    Z.item_of = gs_item.p;
-                    Z.dbg = stamps_begin((size_t)n_blocks * GS * 4 * 8);
-                    last_pass_tile = max_tile_in;
-                    prof.begin(0, stream);
-                    tr("k_forces_gs");
-                    if (req.fuse_spread || req.fuse_terms) {      // … with the charge spreading (PME) and the bonded terms of the step as further workgroups of the same launch
-                        bonded.ensure_roles(stream, cap);
-                        const bool with_spread = req.fuse_spread;
-                        const int order = with_spread ? pme.order : 5;
-                        // inside vv_run: the Σ m v partials of the launch before become one partial in an extra workgroup of this launch (the step's last launch reads four words)
-                        const bool gs_cm_fin = (in_vv_fused || in_lang_fused) && !energy && pending_cm.mode() == 2 && pending_cm.n > 1 && pending_cm.n <= 65536;
-                        if (gs_cm_fin) cm_fin_buf.reserve(4);
-                        const size_t lds = (with_spread ? std::max(gs_lds_bytes(q_lds, BI, JS / GS), std::min<size_t>((size_t)MAX_LDS_BYTES / GS, spread_head_bytes_f32(order) + (size_t)PME_BOX_BYTES)) : gs_lds_bytes(q_lds, BI, JS / GS)) & ~(size_t)15;
-                        const int n_spread = with_spread ? (int)std::min<int64_t>(cdiv(n_owned, (int64_t)64), 4096) : 0;
-                        launch_pair_spread_bonded(Z, n_blocks * GS, coulm, minimg, order, n_owned, reinterpret_cast<float*>(pme.rgrid.p), reinterpret_cast<const PmeP<float>&>(pme.P), n_spread,
-                                                  reinterpret_cast<const BondedArgs<float>&>(static_cast<const BondedArgs<T>&>(bonded.slot_args(G, I, pos[cur].p, inv.p))), cdiv(bonded.n_blocks(), 4), lds, stream,
-                                                  gs_cm_fin ? pending_cm.parts_arg() : (const double*)nullptr, pending_cm.n, gs_cm_fin ? cm_fin_buf.p : (double*)nullptr);
-                        if (gs_cm_fin) pending_cm.moved(cm_fin_buf.p, 1);
-                        res.spread = with_spread; res.terms = !with_spread;
-                    } else launch_forces_gs(Z, coulm, minimg, stream);
-                    prof.end(0, stream);
-                    MHIP_HIP(hipGetLastError());
-                    ++n_force_calls; ++n_gs_passes; res.gs = true;
-                    if (Z.dbg && (n_gs_passes % stamps_every()) == 0) stamps_dump("", (size_t)n_blocks * GS * 4 * 8);      // (stamp builds: tools/gs_times.py)
-                    return res;
-                }
-            }
+        const PassPlan plan = plan_pass(pass_shape(energy, part, allow_gs, req));
+        throw_capacity(plan);
+        if (req.halo && !plan.steps) throw ApiError{MHIP_ERR_STATE, "internal: the fused ghosted step was asked for a pass that cannot integrate"};
+        if (plan.form == PassForm::GROUP_SPLIT) return launch_gs_pass(plan, req);
+        last_plan = plan;
+        PassRes res;
+        ForceArgs<T> A{};      // (every field a pass does not use stays null)
+        fill_block_args(A, plan, part, req.frc);
+        if (plan.prune) arm_prune(A, plan);
+        // inside a step loop: the Σ m v partials of the integrator launch before this pass become one partial here (kernels.h, cm_finalize_in_block)
+        if (plan.cm_fin) { cm_fin_buf.reserve(4); A.cm_fin_in = pending_cm.parts_arg(); A.cm_fin_n = pending_cm.n; A.cm_fin_out = cm_fin_buf.p; }
+        else if (req.cm_sum_in && plan.cm_slot) {      // (mhip_domain_run on one brick: halo_mid's partials)
+            cm_fin_buf.reserve(4); A.cm_fin_in = req.cm_sum_in; A.cm_fin_n = pending_cm.n; A.cm_fin_out = cm_fin_buf.p; res.cm_summed = true;
         }
-        const size_t prune_extra = prune ? prune_lds_bytes(std::min(T_cap, max_tile + 1), BI * JS) + 16 : 0;   // a tile that fills the LDS is segmented a little earlier
-        carve_force_lds(use_inner ? max_tile_in : max_tile, prune_extra);
-        last_pass_tile = use_inner ? max_tile_in : max_tile;
-        A.T_lds = tile_lds;
-        if (use_inner && !inner_is_outer) { A.tile_idx = tile_idx_in.p; A.tile_cnt = tile_cnt_in.p; }
-        A.nbr = (use_inner && !inner_is_outer) ? nbr_in.p : nbr.p; A.wave_rows = (use_inner && !inner_is_outer) ? wave_rows_in.p : wave_rows.p;
-        A.nbr_dst = nullptr; A.rows_dst = nullptr; A.pos_snap = nullptr; A.blk_disp2 = nullptr; A.r_prune2 = r_prune2;
-        A.tile_idx_dst = nullptr; A.tile_cnt_dst = nullptr; A.mark_off = 0; A.snap_dst = nullptr; A.any_special = n_special > 0 ? 1 : 0; A.eshift = eshift;
-        A.cnt_dst = nullptr;
-        A.soa = packed_stride(use_inner ? max_tile_in : max_tile, energy);
-        if (A.soa) lds_force = std::max((size_t)3 * A.soa * sizeof(float) + 64, (size_t)JS * 4 * BI * sizeof(T) + 32);   // x[], y[], z[] instead of the generic 16-byte records
-        A.part = 0; A.blk_ghost = nullptr;
-        if (part != 0 && !prune) {   // blocks without / with ghost atoms in their tile (flags of the tile this pass stages)
-            DBuf<int32_t>& fl = use_inner ? blk_ghost_in : blk_ghost; bool& ok = use_inner ? ghost_flags_in_ok : ghost_flags_ok;
+        A.dbg = (!plan.prune && !energy) ? stamps_begin((size_t)n_blocks * 16 * 8) : nullptr;
+        if (plan.steps) arm_step(A, req);
+        prof.begin(plan.prune ? 4 : 0, stream);   // stage 4 = force passes that also prune the outer list
+        tr(plan.prune ? "k_forces (prune)" : (energy ? "k_forces (energy)" : (plan.steps ? (req.halo ? "k_forces (fused ghosted step)" : "k_forces (fused step)") : "k_forces")));
+        launch_block_pass(A, plan, energy, req);
+        if (plan.steps) { res.step = true; res.parts = n_blocks; }
+        if (plan.cm_fin) pending_cm.moved(cm_fin_buf.p, 1);
+        tr("after k_forces");
+        if (plan.prune && gs_groups() > 0) {      // the list this prune wrote, dealt to the groups (it stays as it is for every other kind of pass)
+            regroup(nbr_in.p, cnt_in.p, tile_cnt_in.p, false);
+            gs_list_id = n_filters + 1;      // (n_filters counts this prune below)
+        }
+        prof.end(plan.prune ? 4 : 0, stream);
+        MHIP_HIP(hipGetLastError());
+        ++n_force_calls;
+        if (A.dbg && (n_force_calls % stamps_every()) == 0) stamps_report();
+        if (plan.prune) finish_prune(xf_direct && n_ghost > 0 && prune_late_env);      // inside mhip_domain_run on a ghosted sub-domain: read behind an event (prune_resolve)
+        return res;
+    }
+
+    // a plain pass over an inner list that has its group-split form, with or without the charge spreading (PME) and the bonded terms of the step as further workgroups of the same launch
+    PassRes launch_gs_pass(const PassPlan& plan, const PassReq& req) {
+        PassRes res;
+        if constexpr (std::is_same<T, float>::value) {
+            const int GS = gs_groups();
+            frc_parts.reserve((size_t)(GS - 1) * cap);
+            GsArgs Z{};
+            Z.G = G; Z.I = I; Z.n_owned = n_owned; Z.BI = BI; Z.BI_shift = ilog2(BI); Z.JS = JS; Z.GS = GS; Z.lgGS = ilog2(GS); Z.R_cap = GS * R_cap;      // (the group-split list's own row capacity: RegroupArgs::R_cap_dst)
+            Z.T_cap = T_cap; Z.Q_lds = plan.q_lds; Z.n_blocks = n_blocks; Z.spread = std::max(1, n_blocks / GS + 5);
+            Z.pos = pos[cur].p; Z.lj = lj[cur].p; Z.tile_idx = inner_is_outer ? tile_idx.p : tile_idx_in.p; Z.tile_cnt = inner_is_outer ? tile_cnt.p : tile_cnt_in.p; Z.nbr = nbr_gs.p; Z.wave_rows = rows_gs.p; Z.blk_center = blk_center.p;
+            Z.frc = frc[cur].p; Z.parts = frc_parts.p; Z.part_stride = cap; Z.item_of = gs_item.p;
+            Z.dbg = stamps_begin((size_t)n_blocks * GS * 4 * 8);
+            last_plan.tile_max = plan.tile_max;
+            prof.begin(0, stream);
+            tr("k_forces_gs");
+            if (req.fuse_spread || req.fuse_terms) {
+                bonded.ensure_roles(stream, cap);
+                const int order = req.fuse_spread ? pme.order : 5;
+                if (plan.cm_fin) cm_fin_buf.reserve(4);      // (an extra workgroup of the launch sums the partials: the step's last launch reads four words)
+                const size_t lds = (req.fuse_spread ? std::max(plan.lds_bytes, std::min<size_t>((size_t)MAX_LDS_BYTES / GS, spread_head_bytes_f32(order) + (size_t)PME_BOX_BYTES)) : plan.lds_bytes) & ~(size_t)15;
+                const int n_spread = req.fuse_spread ? (int)std::min<int64_t>(cdiv(n_owned, (int64_t)64), 4096) : 0;
+                launch_pair_spread_bonded(Z, n_blocks * GS, coulm, minimg, order, n_owned, reinterpret_cast<float*>(pme.rgrid.p), reinterpret_cast<const PmeP<float>&>(pme.P), n_spread,
+                                          reinterpret_cast<const BondedArgs<float>&>(static_cast<const BondedArgs<T>&>(bonded.slot_args(G, I, pos[cur].p, inv.p))), cdiv(bonded.n_blocks(), 4), lds, stream,
+                                          plan.cm_fin ? pending_cm.parts_arg() : (const double*)nullptr, pending_cm.n, plan.cm_fin ? cm_fin_buf.p : (double*)nullptr);
+                if (plan.cm_fin) pending_cm.moved(cm_fin_buf.p, 1);
+                res.spread = req.fuse_spread; res.terms = !req.fuse_spread;
+            } else launch_forces_gs(Z, coulm, minimg, stream);
+            prof.end(0, stream);
+            MHIP_HIP(hipGetLastError());
+            ++n_force_calls; ++n_gs_passes; res.gs = true;
+            if (Z.dbg && (n_gs_passes % stamps_every()) == 0) stamps_dump("", (size_t)n_blocks * GS * 4 * 8);      // (stamp builds: tools/gs_times.py)
+        }
+        return res;
+    }
+
+    // the list the pass walks, its tile, and — a pass over part of a ghosted sub-domain's blocks — the flags that name them
+    void fill_block_args(ForceArgs<T>& A, const PassPlan& plan, int part, T4* own_frc) {
+        A.G = G; A.I = I; A.n_owned = n_owned; A.BI = BI; A.BI_shift = ilog2(BI); A.JS = JS; A.T_cap = T_cap; A.T_lds = plan.tile_lds; A.R_cap = R_cap;
+        A.n_blocks = n_blocks; A.blocks_per_xcd = cdiv(n_blocks, 8);
+        A.pos = pos[cur].p; A.lj = lj[cur].p; A.blk_center = blk_center.p; A.frc = own_frc ? own_frc : frc[cur].p; A.pe_part = red_part.p;
+        const bool pruned = plan.use_inner && !inner_is_outer;      // the pruned list's own arrays (an adopted outer list stays where it was searched)
+        A.tile_idx = pruned ? tile_idx_in.p : tile_idx.p; A.tile_cnt = pruned ? tile_cnt_in.p : tile_cnt.p;
+        A.nbr = pruned ? nbr_in.p : nbr.p; A.wave_rows = pruned ? wave_rows_in.p : wave_rows.p;
+        A.r_prune2 = r_prune2; A.any_special = n_special > 0 ? 1 : 0; A.eshift = eshift; A.soa = plan.soa;
+        if (part != 0 && !plan.prune) {   // blocks without / with ghost atoms in their tile (flags of the tile this pass stages)
+            DBuf<int32_t>& fl = plan.use_inner ? blk_ghost_in : blk_ghost; bool& ok = plan.use_inner ? ghost_flags_in_ok : ghost_flags_ok;
             if (!ok) {
                 fl.reserve(n_blocks);
                 hipLaunchKernelGGL(k_block_ghost_flags, dim3(n_blocks), dim3(WAVE), 0, stream, n_blocks, T_cap, n_owned, (const int32_t*)A.tile_idx, (const int32_t*)A.tile_cnt, fl.p);
@@ -987,56 +984,41 @@ template <class T> class Engine final : public EngineBase {
             }
             A.part = part; A.blk_ghost = fl.p;
         }
-        if (prune) {
-            wave_rows_in.reserve((size_t)n_blocks * JS * (BI / WAVE)); nbr_in.reserve((size_t)n_blocks * JS * R_cap * BI); blk_disp2.reserve((size_t)n_blocks * (BI / WAVE));
-            A.nbr_dst = nbr_in.p; A.rows_dst = wave_rows_in.p; A.pos_snap = pos_snap.p; A.blk_disp2 = blk_disp2.p;
-            pos_snap_in.reserve(cap);
-            // the snapshot the next displacement checks compare with: the owned atoms' by the kernel itself, ghosts by a copy
-            A.snap_dst = pos_snap_in.p;
-            if (n_ghost > 0) MHIP_HIP(hipMemcpyAsync(pos_snap_in.p + n_owned, pos[cur].p + n_owned, (size_t)n_ghost * sizeof(T4), hipMemcpyDeviceToDevice, stream));
-            lp.last_prune_step = pass_step;
-            tile_idx_in.reserve((size_t)n_blocks * T_cap); tile_cnt_in.reserve(n_blocks);
-            A.tile_idx_dst = tile_idx_in.p; A.tile_cnt_dst = tile_cnt_in.p;
-            inner_is_outer = false;
-            if (GS > 0) { cnt_in.reserve((size_t)n_blocks * JS * BI); A.cnt_dst = cnt_in.p; }   // (k_regroup wants the real entries per (sub-list, lane))
-            A.mark_off = (int)((lds_force + 15) & ~(size_t)15);
-            if (A.soa && A.mark_off != prune_mark_ct(A.soa)) throw ApiError{MHIP_ERR_STATE, "internal: the packed pruning pass expects its renumbering table at " + std::to_string(prune_mark_ct(A.soa)) + ", the carve-up put it at " + std::to_string(A.mark_off)};
-            lds_force = (size_t)A.mark_off + prune_lds_bytes(tile_lds, BI * JS);   // + renumbering table + scan scratch + wave boxes
-            if (lds_force > (size_t)MAX_LDS_BYTES) throw ApiError{MHIP_ERR_CAPACITY, "prune pass LDS carve-up exceeds 160 KiB"};
-        }
-        A.blk_center = blk_center.p; A.frc = req.frc ? req.frc : frc[cur].p; A.pe_part = red_part.p;
-        // inside vv_run: the Σ m v partials of the integrator launch before this pass become one partial here (kernels.h, cm_finalize_in_block)
-        A.cm_fin_in = nullptr; A.cm_fin_n = 0; A.cm_fin_out = nullptr;
-        A.vel = nullptr; A.pos_next = nullptr; A.dt = T(0); A.dt2 = T(0); A.cm_in = nullptr; A.cm_n = 0; A.cm_pub = nullptr; A.step_seq = 0; A.cm_out = nullptr; A.trk_part = nullptr; A.snap_a = nullptr; A.snap_b = nullptr;
-        const bool cm_fin = (in_vv_fused || in_lang_fused) && !energy && n_ghost == 0 && part == 0 && pending_cm.mode() == 2 && pending_cm.n > 1 && pending_cm.n <= 65536;      // (the energy variants do not carry the sum)
-        if (cm_fin) { cm_fin_buf.reserve(4); A.cm_fin_in = pending_cm.parts_arg(); A.cm_fin_n = pending_cm.n; A.cm_fin_out = cm_fin_buf.p; }
-        else if (req.cm_sum_in && !energy && n_ghost == 0 && part == 0) {      // (mhip_domain_run on one brick: halo_mid's partials)
-            cm_fin_buf.reserve(4); A.cm_fin_in = req.cm_sum_in; A.cm_fin_n = pending_cm.n; A.cm_fin_out = cm_fin_buf.p; res.cm_summed = true;
-        }
-        A.level_pairs = (prune && JS == 2) ? 1 : 0;      // (an atom's two sub-lists levelled before they are padded: kernels.h)
-        A.dbg = (!prune && !energy) ? stamps_begin((size_t)n_blocks * 16 * 8) : nullptr;
-        // the fused step: this pass also integrates (see PassReq)
-        bool do_step = false;
+    }
+
+    // the pruning pass: where the inner list, its compacted tile and the snapshot of the coordinates it saw go
+    void arm_prune(ForceArgs<T>& A, const PassPlan& plan) {
+        wave_rows_in.reserve((size_t)n_blocks * JS * (BI / WAVE)); nbr_in.reserve((size_t)n_blocks * JS * R_cap * BI); blk_disp2.reserve((size_t)n_blocks * (BI / WAVE));
+        A.nbr_dst = nbr_in.p; A.rows_dst = wave_rows_in.p; A.pos_snap = pos_snap.p; A.blk_disp2 = blk_disp2.p;
+        pos_snap_in.reserve(cap);
+        // the snapshot the next displacement checks compare with: the owned atoms' by the kernel itself, ghosts by a copy
+        A.snap_dst = pos_snap_in.p;
+        if (n_ghost > 0) MHIP_HIP(hipMemcpyAsync(pos_snap_in.p + n_owned, pos[cur].p + n_owned, (size_t)n_ghost * sizeof(T4), hipMemcpyDeviceToDevice, stream));
+        lp.last_prune_step = pass_step;
+        tile_idx_in.reserve((size_t)n_blocks * T_cap); tile_cnt_in.reserve(n_blocks);
+        A.tile_idx_dst = tile_idx_in.p; A.tile_cnt_dst = tile_cnt_in.p;
+        inner_is_outer = false;
+        if (gs_groups() > 0) { cnt_in.reserve((size_t)n_blocks * JS * BI); A.cnt_dst = cnt_in.p; }   // (k_regroup wants the real entries per (sub-list, lane))
+        A.mark_off = plan.mark_off;      // renumbering table + scan scratch + wave boxes behind the tile
+        A.level_pairs = JS == 2 ? 1 : 0;      // (an atom's two sub-lists levelled before they are padded: kernels.h)
+    }
+
+    // the fused step: this pass also integrates (see PassReq) — velocities, the other position buffer, the Σ m v words, a sub-domain's halo tables, the Langevin parameters
+    void arm_step(ForceArgs<T>& A, const PassReq& req) {
+        pos_alt.reserve(cap); cm_blk.reserve(2 * 4 * (size_t)n_blocks + 8);
+        if (!cm_pub.p) { cm_pub.reserve(4); MHIP_HIP(hipMemsetAsync(cm_pub.p, 0, 4 * sizeof(unsigned long long), stream)); }      // (launch numbers start at 1)
+        A.vel = vel[cur].p; A.pos_next = pos_alt.p; A.dt = T(req.dt); A.dt2 = T(req.dt) / T(2);
+        A.cm_in = pending_cm.parts_arg(); A.cm_n = pending_cm.n; A.cm_pub = cm_pub.p; A.step_seq = ++step_seq;      // (the head workgroup of the launch sums the partials)
+        A.cm_out = req.cm ? cm_blk.p + (size_t)step_half * 4 * n_blocks : (double*)nullptr;
+        A.snap_a = pos_snap_in.p; A.snap_b = pos_snap.p;
+        if (req.measure) { trk_reserve(n_blocks); A.trk_part = trk_part.p; }
+        if (req.halo) hx_fill(A, req.halo_cm_in);
+        if (req.lang) { if (req.halo) throw ApiError{MHIP_ERR_STATE, "internal: Langevin update asked of a ghosted step"}; A.orig = orig[cur].p; A.S = *req.lang; }
+    }
+
+    void launch_block_pass(const ForceArgs<T>& A, const PassPlan& plan, bool energy, const PassReq& req) {
         if constexpr (std::is_same<T, float>::value) {
-            do_step = req.step && fuse_step_env && A.soa != 0 && use_inner && !prune && part == 0 && !req.frc && (n_ghost == 0 || req.halo) && pending_cm.mode() != 1;
-            if (req.halo && !do_step) throw ApiError{MHIP_ERR_STATE, "internal: the fused ghosted step was asked for a pass that cannot integrate"};
-            if (do_step) {
-                pos_alt.reserve(cap); cm_blk.reserve(2 * 4 * (size_t)n_blocks + 8);
-                if (!cm_pub.p) { cm_pub.reserve(4); MHIP_HIP(hipMemsetAsync(cm_pub.p, 0, 4 * sizeof(unsigned long long), stream)); }      // (launch numbers start at 1)
-                A.vel = vel[cur].p; A.pos_next = pos_alt.p; A.dt = T(req.dt); A.dt2 = T(req.dt) / T(2);
-                A.cm_in = pending_cm.parts_arg(); A.cm_n = pending_cm.n; A.cm_pub = cm_pub.p; A.step_seq = ++step_seq;
-                A.cm_out = req.cm ? cm_blk.p + (size_t)step_half * 4 * n_blocks : (double*)nullptr;
-                A.trk_part = nullptr; A.snap_a = pos_snap_in.p; A.snap_b = pos_snap.p;
-                if (req.measure) { trk_reserve(n_blocks); A.trk_part = trk_part.p; }
-                A.cm_fin_in = nullptr; A.cm_fin_n = 0; A.cm_fin_out = nullptr;      // (the head workgroup of the launch sums the partials instead)
-                if (req.halo) hx_fill(A, req.halo_cm_in);
-                if (req.lang) { if (req.halo) throw ApiError{MHIP_ERR_STATE, "internal: Langevin update asked of a ghosted step"}; A.orig = orig[cur].p; A.S = *req.lang; }
-            }
-        }
-        prof.begin(prune ? 4 : 0, stream);   // stage 4 = force passes that also prune the outer list
-        tr(prune ? "k_forces (prune)" : (energy ? "k_forces (energy)" : (do_step ? (req.halo ? "k_forces (fused ghosted step)" : "k_forces (fused step)") : "k_forces")));
-        if constexpr (std::is_same<T, float>::value) {
-            if (do_step) {
+            if (plan.steps) {
                 if (req.halo && xf.shared_device && halo_waiter_env) {
                     // Several ranks on ONE device: the peers need the same compute units to produce what this launch would wait for, and a grid of resident,
                     // spinning workgroups can leave their kernels no room (a search kernel's 100 KB of LDS next to two spinning blocks per unit: a 2 s stall,
@@ -1044,57 +1026,56 @@ template <class T> class Engine final : public EngineBase {
                     XferWait W{}; W.mine = reinterpret_cast<const XferHeader*>(xf.region.p); W.parity = (int)(xf.seq & 1u); W.seq = xf.seq; W.peers = xf.d_peers.p; W.n_peers = xf.n_peers; W.err = xf.err.p; W.ticks = xf_ticks();
                     hipLaunchKernelGGL(k_xfer_wait_all, dim3(1), dim3(64), 0, stream, W);
                 }
-                launch_forces_uniform_f32(A, false, false, lds_force, (unsigned)(BI * JS), stream, true, req.halo, req.lang != nullptr);
+                launch_forces_uniform_f32(A, false, false, plan.lds_bytes, (unsigned)(BI * JS), stream, true, req.halo, req.lang != nullptr);
                 if (req.halo) ++xf.seq;      // (the launch's last wave announces exchange xf.seq at the peers)
                 std::swap(pos[cur], pos_alt);      // the epilogues wrote the drifted coordinates into the other buffer: it is the current one now
-                res.step = true; res.parts = n_blocks; ++n_fused_steps;
-            } else launch_forces_any(A, energy);
-        } else launch_forces_any(A, energy);
-        if (cm_fin && !do_step) pending_cm.moved(cm_fin_buf.p, 1);
-        tr("after k_forces");
-        if constexpr (std::is_same<T, float>::value) {
-            if (prune && GS > 0) {      // the list this prune wrote, dealt to the groups (it stays as it is for every other kind of pass)
-                nbr_gs.reserve((size_t)n_blocks * JS * GS * R_cap * BI); rows_gs.reserve((size_t)n_blocks * JS * (BI / WAVE));
-                RegroupArgs R{BI, ilog2(BI), JS, GS, ilog2(GS), R_cap, (const uint2*)nbr_in.p, (const uint16_t*)cnt_in.p, (const int32_t*)tile_cnt_in.p, nbr_gs.p, rows_gs.p,
-                              (int)std::min<size_t>((size_t)MAX_LDS_BYTES - (size_t)JS * BI * 16 - 64, (size_t)JS * R_cap * BI * 8), GS * R_cap};
-                tr("k_regroup");
-                launch_regroup(R, n_blocks, stream);
-                gs_balance();
-                gs_list_id = n_filters + 1;      // (n_filters counts this prune below)
+                ++n_fused_steps;
+                return;
             }
         }
-        prof.end(prune ? 4 : 0, stream);
-        MHIP_HIP(hipGetLastError());
-        ++n_force_calls;
-        if (A.dbg && (n_force_calls % stamps_every()) == 0) stamps_report();
-        if (prune) {   // validity of the pruned list: nobody moved more than half the margin since the outer search
-            // one single-block launch that leaves its figures in pinned host memory (no zeroing launch, no copy launch) …
-            const bool late = xf_direct && n_ghost > 0 && prune_late_env;      // inside mhip_domain_run on a ghosted sub-domain: read behind an event (prune_resolve)
-            if (late) { h_prune.make(N_FLAGS); ev_prune.make(hipEventDisableTiming); }
-            int32_t* const h_dst = late ? h_prune : h_flags;
-            hipLaunchKernelGGL(k_prune_summary, dim3(1), dim3(1024), 0, stream, n_blocks, n_blocks * JS * (BI / WAVE), n_blocks * (BI / WAVE), R_cap,
-                               (const int32_t*)tile_cnt_in.p, wave_rows_in.p, (const float*)blk_disp2.p, flags.p, h_dst);
-            if (n_ghost > 0) {   // … the blocks recorded the displacement of the owned atoms; the ghosts' comes on top
-                hipLaunchKernelGGL(k_max_disp<T>, dim3(std::min(cdiv(n_ghost, 256), 1024)), dim3(256), 0, stream, n_ghost, (const T4*)pos[cur].p + n_owned, (const T4*)pos_snap.p + n_owned,
-                                   reinterpret_cast<unsigned int*>(flags.p + FLAG_MAX_DISP2), G);
-                MHIP_HIP(hipMemcpyAsync(h_dst, flags.p, N_FLAGS * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-            }
-            ++n_filters; ghost_flags_in_ok = false; lp.next_check_step = -1; hx.tile_ok = false; hx.trk_step = -1;
-            inner_valid = true;
-            if (late) {
-                MHIP_HIP(hipEventRecord(ev_prune, stream));
-                prune_pending = true; prune_pending_id = n_filters; prune_disp_exceeded = false;
-                max_tile_in = max_tile;      // (an upper bound until the figures are read: the pruned tile of a block is a subset of its outer tile)
-            } else {
-                MHIP_HIP(hipStreamSynchronize(stream));
-                prune_pending = false;
-                float d2; std::memcpy(&d2, &h_flags[FLAG_MAX_DISP2], sizeof(float));
-                total_rows = h_flags[FLAG_TOTAL_ROWS]; max_tile_in = h_flags[FLAG_MAX_TILE];
-                prune_disp_exceeded = !lp.prune_stands(std::sqrt((double)d2));
-                if (debug_on) std::fprintf(stderr, "[mhip] prune: max disp %.5f nm (margin %.3f) rows %lld exceeded %d calls %lld\n", std::sqrt((double)d2), lp.prune_margin(), (long long)total_rows, (int)prune_disp_exceeded, (long long)n_force_calls);
-            }
+        launch_forces_any(A, plan, energy);
+    }
+
+    // a list — the pruned one, or the outer list as searched — dealt to the groups of the group-split pass (forces_gs.hip, k_regroup), and the groups to the compute units
+    void regroup(const uint2* src, const uint16_t* cnt, const int32_t* tcnt, bool outer) {
+        const int GS = gs_groups();
+        nbr_gs.reserve((size_t)n_blocks * JS * GS * R_cap * BI); rows_gs.reserve((size_t)n_blocks * JS * (BI / WAVE));
+        RegroupArgs R{};
+        R.BI = BI; R.BI_shift = ilog2(BI); R.JS = JS; R.GS = GS; R.lgGS = ilog2(GS); R.R_cap = R_cap; R.src = src; R.cnt = cnt; R.tile_cnt = tcnt; R.dst = nbr_gs.p; R.rows_dst = rows_gs.p;
+        R.lds_list_bytes = regroup_list_bytes(BI, JS, R_cap); R.R_cap_dst = GS * R_cap;
+        if (outer) R.dbg = stamps_begin((size_t)n_blocks * 16 * 8);
+        tr(outer ? "k_regroup (outer list)" : "k_regroup");
+        launch_regroup(R, n_blocks, stream);
+        if (R.dbg) stamps_dump(".regroup", (size_t)n_blocks * 8);
+        gs_balance();
+    }
+
+    // validity of the pruned list: nobody moved more than half the margin since the outer search.  One single-block launch leaves the figures in pinned host memory
+    // (no zeroing launch, no copy launch); they are read here, or — late — behind an event by prune_resolve.
+    void finish_prune(bool late) {
+        if (late) { h_prune.make(N_FLAGS); ev_prune.make(hipEventDisableTiming); }
+        int32_t* const h_dst = late ? h_prune : h_flags;
+        hipLaunchKernelGGL(k_prune_summary, dim3(1), dim3(1024), 0, stream, n_blocks, n_blocks * JS * (BI / WAVE), n_blocks * (BI / WAVE), R_cap,
+                           (const int32_t*)tile_cnt_in.p, wave_rows_in.p, (const float*)blk_disp2.p, flags.p, h_dst);
+        if (n_ghost > 0) {   // … the blocks recorded the displacement of the owned atoms; the ghosts' comes on top
+            hipLaunchKernelGGL(k_max_disp<T>, dim3(std::min(cdiv(n_ghost, 256), 1024)), dim3(256), 0, stream, n_ghost, (const T4*)pos[cur].p + n_owned, (const T4*)pos_snap.p + n_owned,
+                               reinterpret_cast<unsigned int*>(flags.p + FLAG_MAX_DISP2), G);
+            MHIP_HIP(hipMemcpyAsync(h_dst, flags.p, N_FLAGS * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
         }
-        return res;
+        ++n_filters; ghost_flags_in_ok = false; lp.next_check_step = -1; hx.tile_ok = false; hx.trk_step = -1;
+        inner_valid = true;
+        if (late) {
+            MHIP_HIP(hipEventRecord(ev_prune, stream));
+            prune_pending = true; prune_pending_id = n_filters; prune_disp_exceeded = false;
+            max_tile_in = max_tile;      // (an upper bound until the figures are read: the pruned tile of a block is a subset of its outer tile)
+            return;
+        }
+        MHIP_HIP(hipStreamSynchronize(stream));
+        prune_pending = false;
+        float d2; std::memcpy(&d2, &h_flags[FLAG_MAX_DISP2], sizeof(float));
+        total_rows = h_flags[FLAG_TOTAL_ROWS]; max_tile_in = h_flags[FLAG_MAX_TILE];
+        prune_disp_exceeded = !lp.prune_stands(std::sqrt((double)d2));
+        if (debug_on) std::fprintf(stderr, "[mhip] prune: max disp %.5f nm (margin %.3f) rows %lld exceeded %d calls %lld\n", std::sqrt((double)d2), lp.prune_margin(), (long long)total_rows, (int)prune_disp_exceeded, (long long)n_force_calls);
     }
 
     DBuf<double> cm_fin_buf;
@@ -1109,15 +1090,18 @@ template <class T> class Engine final : public EngineBase {
     // as on separate devices.  Safe only while the ranks' grids together fit the device (the small test systems); tests/test_gpu_domain.py runs it to exercise those waits
     const bool halo_waiter_env = env_int("MOLLYHIP_HALO_WAITER", 1) != 0;
     const bool prune_late_env = env_int("MOLLYHIP_PRUNE_LATE", 1) != 0;      // 0: a pruning pass of a ghosted run drains the stream for its summary, as on a single domain (tests compare the two)
-    // Would a plain pass now be the packed one-type loop over a valid inner list — the only pass that can integrate?  (launch_pair_kernel's own conditions, asked
-    // BEFORE the step is put together: the domain loop leaves the unpack, integrator and pack launches out only when the pass will do their work)
+    // Would a plain pass now be one that can integrate — the packed one-type loop over a valid inner list?  The launch's own plan, asked BEFORE the step is put
+    // together: the domain loop leaves the unpack, integrator and pack launches out only when the pass will do their work.  Writes to nothing but what prune_resolve reads in.
     bool packed_step_possible() {
-        if (!fuse_step_env || !dual || !inner_valid || stale || !packed_kind(false)) return false;
+        if (stale) return false;
         prune_resolve(false);
-        if (prune_pending && max_tile_in + 1 >= SOA_STRIDES[2]) prune_resolve(true);      // (the outer list's bound does not fit the packed loop: the pruned list's own figure is needed now)
-        if (max_tile_in + 1 >= SOA_STRIDES[2]) return false;
-        carve_force_lds(max_tile_in);
-        return packed_stride(max_tile_in, false) != 0;
+        PassReq req; req.step = req.halo = true;
+        PassShape s = pass_shape(false, 0, false, req);
+        if (prune_pending && !plan_pass(s).can_step) {      // the outer list's bound stands in for the pruned list's largest tile: if that is all that keeps the pass from integrating, the real figure is needed now
+            s.max_tile_in = 1;
+            if (plan_pass(s).can_step) { prune_resolve(true); s = pass_shape(false, 0, false, req); }
+        }
+        return plan_pass(s).can_step;
     }
 
     // ---- the fused step of a ghosted sub-domain (kernels.h HaloStep; tables: halo_step.h) -------------------------------------------------------------------
@@ -1218,18 +1202,10 @@ template <class T> class Engine final : public EngineBase {
 
     // the outer list, searched at this step with the radius the inner list would be pruned to, becomes the inner list (see inner_is_outer)
     void adopt_outer_list() {
-        const int GS = gs_groups();
         prof.begin(4, stream);
         pos_snap_in.reserve(cap);
         MHIP_HIP(hipMemcpyAsync(pos_snap_in.p, pos[cur].p, (size_t)n_tot * sizeof(T4), hipMemcpyDeviceToDevice, stream));
-        nbr_gs.reserve((size_t)n_blocks * JS * GS * R_cap * BI); rows_gs.reserve((size_t)n_blocks * JS * (BI / WAVE));
-        RegroupArgs R{BI, ilog2(BI), JS, GS, ilog2(GS), R_cap, (const uint2*)nbr.p, (const uint16_t*)cnt_outer.p, (const int32_t*)tile_cnt.p, nbr_gs.p, rows_gs.p,
-                      (int)std::min<size_t>((size_t)MAX_LDS_BYTES - (size_t)JS * BI * 16 - 64, (size_t)JS * R_cap * BI * 8), GS * R_cap};
-        R.dbg = stamps_begin((size_t)n_blocks * 16 * 8);
-        tr("k_regroup (outer list)");
-        launch_regroup(R, n_blocks, stream);
-        if (R.dbg) stamps_dump(".regroup", (size_t)n_blocks * 8);
-        gs_balance();
+        regroup(nbr.p, cnt_outer.p, tile_cnt.p, true);
         prof.end(4, stream);
         MHIP_HIP(hipGetLastError());
         inner_is_outer = true; max_tile_in = max_tile; lp.last_prune_step = pass_step;
@@ -2951,8 +2927,8 @@ template <class T> class Engine final : public EngineBase {
         prune_resolve(true);
         s->n_atoms = n_tot; s->n_owned = n_owned; s->n_ghost = n_ghost; s->n_rebuilds = n_rebuilds; s->n_force_calls = n_force_calls;
         s->n_blocks = n_blocks; s->block_atoms = BI; s->j_split = JS; s->minimg_mode = minimg ? 1 : 0; s->max_tile_atoms = max_tile;
-        s->last_rebuild_ms = last_rebuild_ms; s->lds_bytes = (int64_t)lds_force;
-        s->tile_segments = segmented ? cdiv(std::max(last_pass_tile, 1), std::max(tile_lds, 1)) : 1;
+        s->last_rebuild_ms = last_rebuild_ms; s->lds_bytes = (int64_t)last_plan.lds_bytes;
+        s->tile_segments = last_plan.tile_segments();
         s->n_group_split_passes = n_gs_passes; s->group_split = gs_groups(); s->n_adopted_outer_lists = (int32_t)std::min<int64_t>(n_adopted, INT32_MAX);
         s->n_fused_steps = n_fused_steps; s->n_box_changes = n_box_changes;
         s->n_list_slots = total_rows * 4 * WAVE;

@@ -17,6 +17,7 @@
 // force: group 0 in the force array, the others in side arrays that the per-atom sums of the bonded slots add (bonded.h: the one launch
 // that touches every atom next) — no atomics, the sum of an atom's four partials is taken in fixed order, forces stay bit-reproducible.
 // Same arithmetic per pair as k_forces (pair_eval2 / pair_eval of physics.h); same lists (the inner list of the dual scheme, re-dealt).
+#include "pass_plan.h"
 #include "kernels.h"
 #include "forces_launch.h"
 #include "step_fused.h"
@@ -306,8 +307,6 @@ __global__ void __launch_bounds__(256, 4) k_pair_spread_bonded(GsArgs A, int n_p
     double e = 0;
     bonded_terms<float, false, true>(B, (wg - n_pair - n_spread) * 4 + (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63), 64, e);   // four 64-lane term blocks per workgroup
 }
-
-size_t gs_lds_bytes(int q_lds, int BI, int JSW) { return std::max((size_t)(q_lds + 1) * (sizeof(float4) + sizeof(float2)), (size_t)JSW * 3 * BI * sizeof(float)) + 64; }
 
 void launch_regroup(const RegroupArgs& A, int n_blocks, hipStream_t stream) {
     const size_t lds = 2 * (size_t)A.JS * A.BI * sizeof(unsigned long long) + 16 + (size_t)A.lds_list_bytes;

@@ -28,7 +28,6 @@ struct GsArgs {
     const uint16_t* item_of;                                              // [n_blocks·GS] nullable: which (group · n_blocks + block) workgroup w takes (k_gs_balance)
     unsigned long long* dbg;                                              // builds with -DMHIP_STAMPS=1: [workgroup][wave][8] time stamps (engine: MOLLYHIP_DBG_TIMES, tools/gs_times.py)
 };
-size_t gs_lds_bytes(int q_lds, int BI, int JSW);
 void launch_regroup(const RegroupArgs& A, int n_blocks, hipStream_t stream);
 void launch_gs_balance(const int32_t* rows_gs, int n_blocks, int JS, int GS, int waves_per_sub, int period, uint16_t* item_of, hipStream_t stream);
 void launch_forces_gs(const GsArgs& A, int coulm, bool minimg, hipStream_t stream);

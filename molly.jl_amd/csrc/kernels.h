@@ -12,6 +12,7 @@
 // own force in registers: no atomics, no cross-lane reduction on the hot path, bit-reproducible forces.
 #pragma once
 #include <type_traits>
+#include "pass_plan.h"
 #include "physics.h"
 #include "halo_xfer.h"
 #include "philox.h"
@@ -30,7 +31,6 @@ constexpr uint32_t XL_EXCLUDED = 1u << 30, XL_SPECIAL = 1u << 31, XL_INDEX = (1u
 //   eshift = 2: the tile slot times four = the BYTE offset of the partner's x in the packed loop's x[] / y[] / z[] LDS arrays, no flag
 //               bit (fp32 one-type LJ fluids, which have no special pairs; tiles of up to 16 383 atoms).  The hot loop then spends one
 //               instruction per partner on its LDS address (v_and / v_lshrrev) instead of three (mask, shift, scale).
-constexpr int ESHIFT_SCALED = 2;
 constexpr int SLOT_MAX_SCALED = 16383;
 __host__ __device__ inline uint32_t entry_slot(uint32_t e, int sh) { return sh ? (e >> sh) : (e & 0x7fffu); }
 __host__ __device__ inline uint32_t entry_special(uint32_t e, int sh) { return sh ? 0u : (e >> 15); }
@@ -1329,14 +1329,7 @@ template <class T> struct ForceArgs {
     if (threadIdx.x < 4) { double t = 0; for (int q = 0; q < (int)(blockDim.x >> 6); ++q) t += sh[4 * q + threadIdx.x]; out4[threadIdx.x] = t; }
     __syncthreads();
 }
-// strides the packed loop is compiled for (odd numbers of dwords): tiles of up to stride − 1 atoms, 12·stride bytes of LDS.  The
-// smallest that holds the tile is used: 36 KiB leaves room for four 512-lane blocks per CU, 48 KiB for three (measured: −12 % per pass).
-constexpr int SOA_STRIDES[3] = {2049, 3073, 4097};
-// dynamic LDS a PRUNE pass needs behind its tile: the renumbering table (2 bytes per tile atom of a segment), scan scratch, eight boxes,
-// the atoms' row counts (lane order) and the destination waves' row counts
-// where the packed pruning pass keeps its renumbering table: right behind the three tile arrays of stride `soa` dwords (+ 64 bytes), as launch_pair_kernel carves it
-__host__ __device__ constexpr int prune_mark_ct(int soa) { return (3 * soa * 4 + 64 + 15) & ~15; }
-__host__ __device__ inline size_t prune_lds_bytes(int t_seg, int nthr) { return (size_t)(((t_seg + 8) & ~7) * 2) + ((size_t)nthr + 4) * 4 + 8 * 8 * 4 + ((size_t)nthr + 64) * 4 + 16 * 8 + 32; }   // (+ the 16 byte-permute selectors of the row compaction)
+// (the packed loop's strides SOA_STRIDES, and where a pruning pass keeps its tables — prune_mark_ct, prune_lds_bytes: pass_plan.h)
 
 // (the plain fp32 one-type passes run four 512-lane blocks per CU = eight waves per SIMD, which takes <= 64 VGPRs: held by attribute)
 #ifndef MHIP_FAST_MIN_WAVES
@@ -1701,8 +1694,8 @@ k_forces(ForceArgs<T> A) {
                     if constexpr (PRUNE) {   // (no slot test: the sentinel slot — padding, and everything a lane without an atom holds — lies 10⁴ nm away)
                         // the four new slot numbers are fetched up front, with the coordinates: looked up inside the branches, each kept
                         // entry waited for an LDS round trip of its own
-                        // (round 6: the table sits at a compile-time LDS address behind the three tile arrays — A.mark_off, which the engine forms from the same numbers and
-                        // launch_pair_kernel checks — so an entry's look-up is ONE shift and a read with an immediate offset, and the table holds the new entries themselves:
+                        // (round 6: the table sits at a compile-time LDS address behind the three tile arrays — A.mark_off, which plan_pass forms from the same numbers
+                        // (pass_plan.h; tests/host/pass_plan_check.cpp sweeps that the two agree) — so an entry's look-up is ONE shift and a read with an immediate offset, and the table holds the new entries themselves:
                         // 12 VALU instructions fewer per row of four than base + ((entry >> 2) << 1), read, << 2)
                         typedef __attribute__((address_space(3))) const unsigned short* lds_hptr;
                         auto new_entry = [&](uint32_t o) -> uint32_t { return (uint32_t)*(lds_hptr)(lbase + prune_mark_ct(SOA_STRIDE) + (o >> 1)); };

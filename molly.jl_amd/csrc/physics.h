@@ -196,8 +196,6 @@ template <class T> __device__ inline T ewald_erfc(T ar, T e, int approx) {
     return M<T>::erfc(ar);
 }
 
-enum { LJ_OFF = 0, LJ_DIST = 1, LJ_GENERIC = 2, LJ_DIST_UNIFORM = 3 };   // UNIFORM: every atom has the same σ, ϵ
-
 // Sum over pairwise_inters for one pair (force.jl:79-92 / kernels.jl:3-17).  Returns `fr` such that the
 // force on atom j is fr·dr (and −fr·dr on atom i, force.jl:873-874) and, if ENERGY, adds the pair energy.
 // PRE_E (the fp32 loops): ei, ej arrive as √ϵ — 0 for an atom with σ = 0 —, taken once per staged atom instead of once per pair.
