@@ -43,7 +43,7 @@
  *   MOLLYHIP_FUSE_STEP=0           plain pair passes write forces and a separate launch integrates (default: the pass integrates in its epilogue)
  *   MOLLYHIP_FUSE_GATHER_VV=0      the same for a small system's last force launch
  *   MOLLYHIP_REUSE_RUN_FORCES=0    every run recomputes the forces of its first step (see mhip_vv_run)
- *   MOLLYHIP_PME_FFT=0|1           PME transforms through hipFFT never / always (default: meshes with more than 512 points on an axis)
+ *   MOLLYHIP_PME_FFT=0|1           PME transforms through hipFFT never / always (default: meshes with more than 512 points on an axis); read whenever a context's PME is set up, mhip_stats.pme_fft says which
  *   MOLLYHIP_DEVICE_REPLAN=0       mhip_domain_run returns to the host planner for every re-plan (see mhip_set_domain)
  *   MOLLYHIP_HALO_WAITER=0         ranks sharing ONE device (tests): no one-workgroup waiter in front of a fused ghosted step; the blocks' own bounded waits order it, as across devices
  *   MOLLYHIP_PRUNE_LATE=0          inside mhip_domain_run a pruning pass of a ghosted sub-domain drains the stream for its summary instead of reading it behind an event
@@ -165,6 +165,7 @@ typedef struct mhip_stats {
     int64_t build_pass_bytes;      /* ONE outer search: N·4w read + 2·n_outer_slots + 4·outer_tile_atoms_total written                */
     int64_t prune_pass_bytes;      /* ONE pruning force pass: N(R_p + 3w) + 2·n_outer_slots + 4·outer tile read, 2·n_list_slots + 4·tile_atoms_total + N·4w (snapshot) written */
     int64_t n_box_changes;         /* boundaries taken over by mhip_set_box (a barostat's trial moves, accepted or taken back)      */
+    int32_t pme_fft;               /* which transforms the PME of this context runs: 0 the direct-DFT passes (and without PME), 1 the FFT library (hipFFT)   */
 } mhip_stats;
 
 /* ---- lifetime ------------------------------------------------------------------------------ */

@@ -2930,7 +2930,7 @@ template <class T> class Engine final : public EngineBase {
         s->last_rebuild_ms = last_rebuild_ms; s->lds_bytes = (int64_t)last_plan.lds_bytes;
         s->tile_segments = last_plan.tile_segments();
         s->n_group_split_passes = n_gs_passes; s->group_split = gs_groups(); s->n_adopted_outer_lists = (int32_t)std::min<int64_t>(n_adopted, INT32_MAX);
-        s->n_fused_steps = n_fused_steps; s->n_box_changes = n_box_changes;
+        s->n_fused_steps = n_fused_steps; s->n_box_changes = n_box_changes; s->pme_fft = pme.on() && pme.fft ? 1 : 0;
         s->n_list_slots = total_rows * 4 * WAVE;
         if (!stale) {
             std::vector<int32_t> tc(n_blocks);

@@ -104,8 +104,14 @@ __device__ inline void pme_atom_tables(int64_t a0, int64_t n_atoms, const typena
 // The LDS sub-mesh accumulates in 64-bit FIXED POINT: on gfx950 ds_add_f32 runs at a tenth of the rate of ds_add_u32 / ds_add_u64
 // (tools/micro/lds_atomic_rate.hip: 8 000 adds of this access pattern per block take 22.6 µs as floats, 6.7 µs — launch included — as
 // 64-bit integers), and the LDS adds were half of the spreading kernel.  A contribution q·w (|w| ≤ 0.3 for orders 4–6) is scaled by
-// 2²⁸ (fp32: resolution 3.7e-9; a batch with a charge beyond 24 e takes the direct path) or 2⁴⁴ (fp64: 5.7e-14), rounded once, sign-extended and added as an unsigned 64-bit word
-// (two's complement: no overflow within 2³⁵ such terms); the sums themselves are then exact and independent of the order of the adds.
+// 2²⁸ (fp32: resolution 3.7e-9; a batch with a charge beyond 24 e takes the direct path) or 2⁵² (fp64: 2.2e-16), rounded once, sign-extended and added as an unsigned 64-bit word
+// (two's complement; a cell receives at most one term per atom of the batch, 64 terms of at most 24·(2/3)³ = 7.1: 2⁶¹ in fp64); the sums themselves are then exact and
+// independent of the order of the adds.
+// The resolution is ABSOLUTE, so what the rounding costs depends on the size of the charges.  fp32, charges of a fluid of |q| ≈ 0.5 e scaled down (the rounding emulated in
+// the CPU oracle, as a share of the largest reciprocal-space force): 4.6e-6 at 2⁻⁸ (|q| ≈ 2e-3 e; the device's whole error there measures 7.0e-6 against the bar of 2e-4),
+// 7.5e-5 at 2⁻¹² and 1.3e-3 at 2⁻¹⁶ — charges below about 1e-4 e are outside what the fp32 sub-mesh resolves to the bar.  The largest term it is handed is
+// 24·(2/3)³·2²⁸ = 1.91e9 (order 4, |q| = 24 on a mesh node), 11 % below the saturation of __float2int_rn.  fp64 carried 2⁴⁴ until the scaled-charge test
+// (tests/test_gpu_pme_edges.py) measured 1.9e-11 in the energy at 2⁻⁸ against the bar of 1e-11; 2⁵² is the resolution of a double of that size.
 constexpr int PME_BOX_BYTES = 48 * 1024;   // LDS sub-mesh, 8 bytes per point
 template <class T> struct PmeFix;
 template <> struct PmeFix<float> {
@@ -113,7 +119,7 @@ template <> struct PmeFix<float> {
     __device__ static inline unsigned long long enc(float v) { return (unsigned long long)(long long)__float2int_rn(v * scale); }
 };
 template <> struct PmeFix<double> {
-    static constexpr double scale = 17592186044416.0, inv = 1.0 / 17592186044416.0;  // 2^44
+    static constexpr double scale = 4503599627370496.0, inv = 1.0 / 4503599627370496.0;  // 2^52
     __device__ static inline unsigned long long enc(double v) { return (unsigned long long)__double2ll_rn(v * scale); }
 };
 #ifndef MHIP_SPREAD_EXP
@@ -696,7 +702,9 @@ template <class T> struct Pme {
         }
         // Past 512 points on an axis the passes above would quietly take tens of milliseconds; such meshes (100 nm boxes) go through the FFT library instead
         // (pme_fft.h: hipFFT real ↔ complex 3-D plans on the same half spectrum), with the influence function as a pass of its own.
-        static const int fft_env = [] { const char* v = std::getenv("MOLLYHIP_PME_FFT"); return v && *v ? std::atoi(v) : -1; }();
+        // (read at every set-up, like the engine's other switches when a context is made: a process can hold contexts of either path)
+        const char* fft_var = std::getenv("MOLLYHIP_PME_FFT");
+        const int fft_env = fft_var && *fft_var ? std::atoi(fft_var) : -1;
         const bool long_axis = mesh[0] > 512 || mesh[1] > 512 || mesh[2] > 512;
         if (long_axis && fft_env == 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "PME mesh axis beyond 512 points needs the FFT path (MOLLYHIP_PME_FFT=0 turned it off)"};
         if ((int64_t)mesh[0] * mesh[1] * mesh[2] > ((int64_t)1 << 30)) throw ApiError{MHIP_ERR_CAPACITY, "PME mesh too large"};
