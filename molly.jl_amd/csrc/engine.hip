@@ -22,6 +22,7 @@
 #include "hilbert.h"
 #include "kernels.h"
 #include "list_policy.h"
+#include "held.h"
 #include "replan.h"
 #include "halo_step.h"
 #include "forces_launch.h"
@@ -184,7 +185,6 @@ template <class T> class Engine final : public EngineBase {
     DBuf<int32_t> tile_idx, tile_cnt, wave_rows; DBuf<uint2> nbr; DBuf<T4> blk_center;
     // dual pair list: outer list (nbr / wave_rows, radius r_list + margin) and the inner list filtered from it
     DBuf<int32_t> wave_rows_in, tile_idx_in, tile_cnt_in, rows_x, tile_idx_x, tile_cnt_x; DBuf<uint2> nbr_in, nbr_x; DBuf<T4> pos_snap; DBuf<float> blk_disp2; int max_tile_in = 0;
-    bool inner_valid = false, prune_disp_exceeded = false;
     // entries per (sub-list, lane) of the inner list as the last prune wrote it / of the outer list as the search wrote it: what k_regroup deals to the groups
     DBuf<uint16_t> cnt_in, cnt_outer; bool cnt_outer_valid = false;
     // the group-split pair pass of small systems (forces_gs.hip): the inner list re-dealt into GS groups per block after every prune, the
@@ -206,7 +206,6 @@ template <class T> class Engine final : public EngineBase {
         return want;
     }
     DBuf<int32_t> blk_ghost, blk_ghost_in; bool ghost_flags_ok = false, ghost_flags_in_ok = false;
-    bool interior_done = false;      // halo_interior ran the blocks without ghosts: the next step_forces (halo_end, a separate call) runs the rest
     int64_t pass_step = 0;       // the MD step whose coordinates the pair pass being launched sees (recorded as the step of a prune)
     DBuf<T4> pos_snap_in;        // coordinates at the last prune (validity of the inner list: 2·displacement <= skin)
     // when a list may live on, is pruned again, is searched again: the rule and the numbers it goes by (list_policy.h)
@@ -255,8 +254,8 @@ template <class T> class Engine final : public EngineBase {
     // (or fold_side_forces) adds it.  (Side streams, CU-masked streams and any-order launches for these chains all measured slower than one stream: DESIGN §4.)
     DBuf<T4> frc_side; const T4* pend_a = nullptr;
 
-    bool stale = true, minimg = false, params_set = false, state_set = false, frc_valid = false;
-    bool coords_moved = false, export_needs_search = false; int64_t n_set_state_refresh = 0;
+    Held held;      // what the context holds and what voids it: changed only through its events (held.h)
+    bool minimg = false; int64_t n_set_state_refresh = 0;
     int64_t last_build_step = std::numeric_limits<int64_t>::min();
     int64_t n_rebuilds = 0, n_force_calls = 0, n_gs_passes = 0; double last_rebuild_ms = 0;
     PassPlan last_plan;      // what the last block pass launched with (pass_plan.h); a group-split pass, which stages no such tile, leaves only its tile_max
@@ -438,7 +437,7 @@ template <class T> class Engine final : public EngineBase {
         estimate_capacities();
     }
     // a new launch shape (and cell grid): every list is void
-    void reblock() { choose_blocking(); stale = true; }
+    void reblock() { choose_blocking(); held.lists_voided(); }
     void regrid() { setup_grid(); reblock(); }
     int rebuild_every() const { return cfg.rebuild_every > 0 ? cfg.rebuild_every : 10; }
 
@@ -461,7 +460,7 @@ template <class T> class Engine final : public EngineBase {
     // two HIP events.  Shapes whose tile does not fit the LDS, or that the build had to shrink, are reported with us_per_pass < 0 /
     // under the shape they ended in.  A shape set by mhip_set_launch_config is replaced by the winner.
     int tune_launch(int n_passes, mhip_launch_trial* trials, int max_trials) override {
-        if (!state_set || !params_set) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before tuning"};
+        if (!held.state_set() || !held.params_set()) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before tuning"};
         if (n_ghost > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "launch shapes are tuned on single-domain contexts (the ranks of a decomposition must agree on one)"};
         if (n_passes < 1) throw ApiError{MHIP_ERR_INVALID, "n_passes must be positive"};
         static const int cand[][2] = {{256, 4}, {256, 2}, {128, 8}, {128, 4}, {128, 2}, {64, 16}, {64, 8}};
@@ -480,7 +479,7 @@ template <class T> class Engine final : public EngineBase {
                 reblock(); lp.cur_dt = 0;
                 ensure_built(step); pass_step = step;
                 launch_pair_kernel(false);                     // with a dual list: the pruning pass
-                if (prune_disp_exceeded) { after_forces(step); launch_pair_kernel(false); }
+                if (held.prune_disp_exceeded()) { after_forces(step); launch_pair_kernel(false); }
                 launch_pair_kernel(false);
                 MHIP_HIP(hipEventRecord(e0, stream));
                 for (int k = 0; k < n_passes; ++k) launch_pair_kernel(false);
@@ -496,7 +495,7 @@ template <class T> class Engine final : public EngineBase {
             if (us > 0 && (best_bi == 0 || us < best)) { best = us; best_bi = BI; best_js = JS; }
         }
         user_bi = best_bi; user_js = best_js;                  // (0, 0 = automatic, when nothing could be timed)
-        reblock(); frc_valid = false;
+        reblock(); held.forces_partial();
         return n;
     }
 
@@ -562,7 +561,7 @@ template <class T> class Engine final : public EngineBase {
     void rebuild_impl(int64_t step_n) {
         lp.next_check_step = -1;
         const int sub_bits = (ilog2(2 * G.ncell + 1) + 1 + 6 <= 32) ? 6 : 0;      // atoms of a cell ordered by a 6-bit Morton position inside it
-        if (!params_set || !state_set) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before forces"};
+        if (!held.params_set() || !held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before forces"};
         auto t0 = std::chrono::steady_clock::now();
         const int o = cur, n = 1 - cur;
         const int ncell2 = 2 * G.ncell + 1;
@@ -657,7 +656,7 @@ template <class T> class Engine final : public EngineBase {
         if (dual) {   // remember where everybody was; the next force pass prunes the outer list into the inner one
             pos_snap.reserve(cap);
             MHIP_HIP(hipMemcpyAsync(pos_snap.p, pos[cur].p, (size_t)n_tot * sizeof(T4), hipMemcpyDeviceToDevice, stream));
-            inner_valid = false; inner_is_outer = false; prune_disp_exceeded = false; ghost_flags_in_ok = false;
+            inner_is_outer = false; ghost_flags_in_ok = false;
             if (lp.cur_dt > 0 && lp.skin_in < lp.skin && !host_prune) {   // inside a run: how fast is the fastest atom? (sizes the inner skin before the first prune)
                 (void)max_disp2_since(pos_snap);
                 const double drift = lp.drift_ahead(0.0, 1, rebuild_every());
@@ -669,8 +668,8 @@ template <class T> class Engine final : public EngineBase {
             MHIP_HIP(hipMemcpyAsync(pos_snap_in.p, pos[cur].p, (size_t)n_tot * sizeof(T4), hipMemcpyDeviceToDevice, stream));
             lp.last_prune_step = step_n;
         }
-        stale = false; coords_moved = false; export_needs_search = false; ghost_flags_ok = false; ghost_flags_in_ok = false; last_build_step = step_n; ++n_rebuilds;
-        frc_run_total = false;   // the sort moved the atoms
+        held.lists_searched(dual);
+        ghost_flags_ok = false; ghost_flags_in_ok = false; last_build_step = step_n; ++n_rebuilds;
         hx.plan_ok = hx.tile_ok = false; hx.trk_step = -1;
         last_rebuild_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
@@ -718,7 +717,7 @@ template <class T> class Engine final : public EngineBase {
     // the policy grew the inner skin: the prune radius follows, and the list pruned with the old one is done with
     void inner_skin_grown(double drift_per_interval) {
         set_prune_radius();
-        inner_valid = false;
+        held.prune_wanted();
         if (debug_on) std::fprintf(stderr, "[mhip] inner skin raised to %.3f nm (drift per check interval %.4f nm)\n", lp.skin_in, drift_per_interval);
     }
 
@@ -730,11 +729,11 @@ template <class T> class Engine final : public EngineBase {
     // s + 1 (with that step of headroom in the outer-list test).  (Taking the maxima inside k_forces instead cost its packed loop
     // 14 % through a different register assignment, with the same instructions: measured, dropped.)
     DBuf<float> trk_part, trk_out; Pinned<float> h_trk; Event ev_trk;
-    bool trk_issued = false; int64_t trk_step = -1, trk_prune_id = -1, trk_outer_id = -1; double trk_prev_vmax = 0;   // (ids: the running counts of prunes / outer searches)
+    int64_t trk_step = -1, trk_prune_id = -1, trk_outer_id = -1; double trk_prev_vmax = 0;   // (ids: the running counts of prunes / outer searches)
     bool in_vv_fused = false;      // inside the fused step loop of vv_loop (async_ok and the pair pass's Σ m v summing read it)
     bool in_lang_fused = false;      // inside mhip_langevin_run of a small system whose last force launch integrates (the pair launch's extra workgroup then sums the Σ m v partials, as inside mhip_vv_run)
     bool in_lang_async = false;      // … and whose list checks are measured by that launch (no Andersen coupling behind it: the speeds the check reads would not be the run's)
-    bool async_ok() const { return (in_vv_fused || in_lang_async) && dual && n_ghost == 0 && !host_prune && inner_valid && !stale; }
+    bool async_ok() const { return (in_vv_fused || in_lang_async) && dual && n_ghost == 0 && !host_prune && held.inner_list_stands(); }
     // room for the per-block maxima of a check measured by n_parts blocks
     void trk_reserve(int n_parts) { trk_part.reserve(3 * (size_t)std::max(n_parts, 1024)); trk_out.reserve(4); }
     // the check of `step` from the n_parts per-block maxima in trk_part: reduce, copy, event
@@ -742,20 +741,20 @@ template <class T> class Engine final : public EngineBase {
         h_trk.make(4); ev_trk.make(hipEventDisableTiming);
         hipLaunchKernelGGL(k_track_reduce, dim3(1), dim3(256), 0, stream, n_parts, (const float*)trk_part.p, trk_out.p, h_trk);   // (straight into pinned host memory)
         MHIP_HIP(hipEventRecord(ev_trk, stream));
-        trk_issued = true; trk_step = step; trk_prev_vmax = lp.last_vmax; trk_prune_id = n_filters; trk_outer_id = n_outer;
+        held.check_issued(); trk_step = step; trk_prev_vmax = lp.last_vmax; trk_prune_id = n_filters; trk_outer_id = n_outer;
     }
     void resolve_track(int64_t step) {
-        if (!trk_issued) return;
+        if (!held.trk_issued()) return;
         MHIP_HIP(hipEventSynchronize(ev_trk));
-        trk_issued = false;
+        held.check_read();
         const ListPolicy::Measured m{std::sqrt((double)h_trk[0]), std::sqrt((double)h_trk[1]), trk_step - lp.last_prune_step};
         lp.measured(std::sqrt((double)h_trk[2]), trk_prev_vmax);   // (the speed of the check before, as it was when this one was issued: a run cut into chunks decides alike)
-        if (!dual || stale || !inner_valid || n_ghost > 0 || n_filters != trk_prune_id || n_outer != trk_outer_id) return;   // the lists it measured have been replaced meanwhile
+        if (!dual || !held.inner_list_stands() || n_ghost > 0 || n_filters != trk_prune_id || n_outer != trk_outer_id) return;   // the lists it measured have been replaced meanwhile
         if (debug_on) std::fprintf(stderr, "[mhip] step %lld: measured at %lld: d %.5f d_outer %.5f v_max %.4f\n", (long long)step, (long long)trk_step, m.d, m.d_outer, lp.last_vmax);
         const ListPolicy::Decision r = lp.decide(m, ListPolicy::Applied::asynchronous(rebuild_every(), trk_step, step));
         if (r.grown) inner_skin_grown(r.ahead);
         if (r.action == ListPolicy::SEARCH) rebuild(step);
-        else if (r.action == ListPolicy::PRUNE) inner_valid = false;
+        else if (r.action == ListPolicy::PRUNE) held.prune_wanted();
     }
 
     bool in_run = false;      // inside a run that owns its step loop (only there may a decision of refresh ask for a check between the cadence steps)
@@ -769,36 +768,36 @@ template <class T> class Engine final : public EngineBase {
             if (debug_on) std::fprintf(stderr, "[mhip] outer margin dropped (inner skin %.3f nm leaves it no second prune)\n", lp.skin_in);
             margin_zero = true; regrid();
         }
-        if (!dual && lazy_single && !stale && step_n > lp.last_prune_step) {
+        if (!dual && lazy_single && !held.stale() && step_n > lp.last_prune_step) {
             // single list built with r_list at step last_prune_step: it still holds every pair within the cutoffs unless somebody moved skin/2
             const ListPolicy::Measured m{std::sqrt((double)max_disp2_since(pos_snap_in)), 0.0, step_n - lp.last_prune_step};
             if (debug_on) std::fprintf(stderr, "[mhip] step %lld: max disp %.5f nm since the build of step %lld (skin %.3f), v_max %.4f\n", (long long)step_n, m.d, (long long)lp.last_prune_step, lp.skin, lp.last_vmax);
             if (lp.decide(m, ListPolicy::Applied::lazy_single(every, step_n, in_run)).action != ListPolicy::SEARCH) { last_build_step = step_n; return; }
         }
-        if (!dual || stale || (n_ghost == 0 && step_n < lp.last_outer_step)) { rebuild(step_n); return; }
+        if (!dual || held.stale() || (n_ghost == 0 && step_n < lp.last_outer_step)) { rebuild(step_n); return; }
         // The inner list (pairs within r_list when it was pruned) provably contains every pair within the cutoffs as long as no atom
         // moved more than skin/2 since then — the condition the reference's fixed cadence only assumes.  Check it; re-prune (inside
         // the next force pass) only when it is about to fail.  mhip_export_neighbors always returns the exact list of NOW.
-        if (host_prune && inner_valid) { last_build_step = step_n; ++n_rebuilds; return; }   // the host calls mhip_request_prune
-        if (inner_valid && trk_issued && trk_step == step_n && async_ok()) {   // measured by the integrator launch that made these coordinates; decided one step later
+        if (host_prune && held.inner_valid()) { last_build_step = step_n; ++n_rebuilds; return; }   // the host calls mhip_request_prune
+        if (held.inner_valid() && held.trk_issued() && trk_step == step_n && async_ok()) {   // measured by the integrator launch that made these coordinates; decided one step later
             last_build_step = step_n; ++n_rebuilds;
             return;
         }
         // the displacement since the prune now; the one since the outer search only if the decision comes to a prune (a ghosted
         // sub-domain's outer list is its ghost plan's: the host vouches for it, mhip_plan_disp2_dev)
-        const ListPolicy::Measured m{inner_valid ? std::sqrt((double)max_disp2_since(pos_snap_in)) : (double)INFINITY, 0.0, step_n - lp.last_prune_step};
+        const ListPolicy::Measured m{held.inner_valid() ? std::sqrt((double)max_disp2_since(pos_snap_in)) : (double)INFINITY, 0.0, step_n - lp.last_prune_step};
         const ListPolicy::Decision r = lp.decide(m, ListPolicy::Applied::synchronous(every, step_n, in_run, n_ghost > 0),
                                                  [&] { return n_ghost > 0 ? 0.0 : std::sqrt((double)max_disp2_since(pos_snap)); });
         if (r.grown) inner_skin_grown(r.ahead);
         if (r.action == ListPolicy::SEARCH) { rebuild(step_n); return; }
-        if (r.action == ListPolicy::PRUNE) inner_valid = false;         // the next force pass re-prunes the outer list at the then-current coordinates
+        if (r.action == ListPolicy::PRUNE) held.prune_wanted();         // the next force pass re-prunes the outer list at the then-current coordinates
         last_build_step = step_n; ++n_rebuilds;
     }
 
     // after a force pass that pruned: if an atom outran half the margin the outer list can no longer vouch for the inner one
     void after_forces(int64_t step_n) {
-        if (!prune_disp_exceeded) return;
-        prune_disp_exceeded = false;
+        if (!held.prune_disp_exceeded()) return;
+        held.outrun_taken();
         if (n_ghost > 0) throw ApiError{MHIP_ERR_STATE, "an atom moved more than half the ghost margin since the ghost plan: re-plan earlier (mhip_plan_disp2_dev)"};
         if (lp.outer_outrun(step_n, rebuild_every())) { if (debug_on) std::fprintf(stderr, "[mhip] dual list off (outer list outrun 3x)\n"); dual_disabled = true; regrid(); }
         rebuild(step_n);
@@ -808,18 +807,17 @@ template <class T> class Engine final : public EngineBase {
     // searches afresh there; a fresh search changes results only where list MEMBERSHIP matters (an interaction without a cutoff
     // inside r_list).  Lists that carry a skin are kept if the displacement checks say they still cover every cutoff sphere: a run
     // continued in chunks then walks the same lists in the same order as the uncut run and reproduces it bit for bit.
-    bool vel_check_due = false;   // velocities were replaced since the last validity check of the lists
     void start_lists(int64_t first_step) {
         lists_after_set_state();
-        if (stale || !(dual || lazy_single)) { vel_check_due = false; rebuild(first_step); return; }
-        if ((lp.check_due(first_step, rebuild_every()) && first_step != last_build_step) || vel_check_due) { vel_check_due = false; refresh(first_step); }
+        if (held.stale() || !(dual || lazy_single)) { held.vel_check_taken(); rebuild(first_step); return; }
+        if ((lp.check_due(first_step, rebuild_every()) && first_step != last_build_step) || held.vel_check_due()) { held.vel_check_taken(); refresh(first_step); }
     }
 
     void ensure_built(int64_t step_n) {
         resolve_track(step_n);
         lists_after_set_state();
-        vel_check_due = false;   // (driven from outside there is no time step: the displacement checks of set_state are all there is)
-        if (stale) rebuild(step_n);
+        held.vel_check_taken();   // (driven from outside there is no time step: the displacement checks of set_state are all there is)
+        if (held.stale()) rebuild(step_n);
         else if (lp.check_due(step_n, rebuild_every()) && step_n != last_build_step) refresh(step_n);
     }
 
@@ -828,13 +826,13 @@ template <class T> class Engine final : public EngineBase {
     // idled while its host woke up and queued the rest of the step): the summary kernel writes into pinned words of their own behind an event; until the host finds the
     // event complete the next passes are shaped for the OUTER list's largest tile (a pruned tile is a subset of it: same results, a larger LDS carve-up for a step or
     // two), and a displacement beyond the ghost margin — which fails the run on this path anyway (after_forces) — is reported when it is read, a step or two later.
-    Pinned<int32_t> h_prune; Event ev_prune; bool prune_pending = false; int64_t prune_pending_id = -1;
+    Pinned<int32_t> h_prune; Event ev_prune; int64_t prune_pending_id = -1;
     void prune_resolve(bool block) {
-        if (!prune_pending) return;
+        if (!held.prune_pending()) return;
         if (!block && hipEventQuery(ev_prune) != hipSuccess) { (void)hipGetLastError(); return; }
         MHIP_HIP(hipEventSynchronize(ev_prune));
-        prune_pending = false;
-        if (n_filters != prune_pending_id || stale || !inner_valid) return;      // the list it described has been replaced meanwhile
+        held.prune_read();
+        if (n_filters != prune_pending_id || !held.inner_list_stands()) return;      // the list it described has been replaced meanwhile
         float d2; std::memcpy(&d2, &h_prune[FLAG_MAX_DISP2], sizeof(float));
         total_rows = h_prune[FLAG_TOTAL_ROWS]; max_tile_in = h_prune[FLAG_MAX_TILE];
         if (debug_on) std::fprintf(stderr, "[mhip] prune (read late): max disp %.5f nm (margin %.3f) rows %lld tile %d\n", std::sqrt((double)d2), lp.prune_margin(), (long long)total_rows, max_tile_in);
@@ -879,7 +877,7 @@ template <class T> class Engine final : public EngineBase {
         PassShape s;
         s.fp32 = std::is_same<T, float>::value; s.ljm = ljm; s.coulm = coulm; s.minimg = minimg; s.n_special = n_special > 0 ? 1 : 0; s.eshift = eshift; s.lj_c12 = I.lj_c12 != T(0);
         s.BI = BI; s.JS = JS; s.T_cap = T_cap; s.lds_budget = (size_t)env_int("MOLLYHIP_LDS_BUDGET_KB", 160) * 1024;
-        s.dual = dual; s.inner_valid = inner_valid; s.max_tile = max_tile; s.max_tile_in = max_tile_in;
+        s.dual = dual; s.inner_valid = held.inner_valid(); s.max_tile = max_tile; s.max_tile_in = max_tile_in;
         s.gs = gs_groups(); s.gs_list_current = gs_list_id == n_filters; s.n_ghost = n_ghost;
         s.energy = energy; s.part = part; s.allow_gs = allow_gs; s.own_frc = req.frc != nullptr;
         s.step = req.step; s.halo = req.halo; s.fuse_step = fuse_step_env;
@@ -894,7 +892,7 @@ template <class T> class Engine final : public EngineBase {
         // dual pair list: a force pass whose inner list is stale walks the OUTER list (always a valid superset — the cutoff is applied per pair) and, if it is a
         // plain force call, prunes it into the inner list on the way — unless the outer list, searched at this very step with the prune radius, can be adopted as it is
         if constexpr (std::is_same<T, float>::value) {
-            if (dual && !inner_valid && !energy && allow_gs && part == 0 && !req.frc && adopt_env && gs_groups() > 0 && cnt_outer_valid && margin_zero && !(lp.skin_in < lp.skin)
+            if (dual && !held.inner_valid() && !energy && allow_gs && part == 0 && !req.frc && adopt_env && gs_groups() > 0 && cnt_outer_valid && margin_zero && !(lp.skin_in < lp.skin)
                 && lp.last_outer_step == pass_step && n_ghost == 0 && !host_prune) adopt_outer_list();
         }
         const PassPlan plan = plan_pass(pass_shape(energy, part, allow_gs, req));
@@ -1063,19 +1061,17 @@ template <class T> class Engine final : public EngineBase {
             MHIP_HIP(hipMemcpyAsync(h_dst, flags.p, N_FLAGS * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
         }
         ++n_filters; ghost_flags_in_ok = false; lp.next_check_step = -1; hx.tile_ok = false; hx.trk_step = -1;
-        inner_valid = true;
         if (late) {
             MHIP_HIP(hipEventRecord(ev_prune, stream));
-            prune_pending = true; prune_pending_id = n_filters; prune_disp_exceeded = false;
+            held.inner_list_made(Held::Prune::READ_LATE); prune_pending_id = n_filters;
             max_tile_in = max_tile;      // (an upper bound until the figures are read: the pruned tile of a block is a subset of its outer tile)
             return;
         }
         MHIP_HIP(hipStreamSynchronize(stream));
-        prune_pending = false;
         float d2; std::memcpy(&d2, &h_flags[FLAG_MAX_DISP2], sizeof(float));
         total_rows = h_flags[FLAG_TOTAL_ROWS]; max_tile_in = h_flags[FLAG_MAX_TILE];
-        prune_disp_exceeded = !lp.prune_stands(std::sqrt((double)d2));
-        if (debug_on) std::fprintf(stderr, "[mhip] prune: max disp %.5f nm (margin %.3f) rows %lld exceeded %d calls %lld\n", std::sqrt((double)d2), lp.prune_margin(), (long long)total_rows, (int)prune_disp_exceeded, (long long)n_force_calls);
+        held.inner_list_made(Held::Prune::READ_NOW, !lp.prune_stands(std::sqrt((double)d2)));
+        if (debug_on) std::fprintf(stderr, "[mhip] prune: max disp %.5f nm (margin %.3f) rows %lld exceeded %d calls %lld\n", std::sqrt((double)d2), lp.prune_margin(), (long long)total_rows, (int)held.prune_disp_exceeded(), (long long)n_force_calls);
     }
 
     DBuf<double> cm_fin_buf;
@@ -1093,11 +1089,11 @@ template <class T> class Engine final : public EngineBase {
     // Would a plain pass now be one that can integrate — the packed one-type loop over a valid inner list?  The launch's own plan, asked BEFORE the step is put
     // together: the domain loop leaves the unpack, integrator and pack launches out only when the pass will do their work.  Writes to nothing but what prune_resolve reads in.
     bool packed_step_possible() {
-        if (stale) return false;
+        if (held.stale()) return false;
         prune_resolve(false);
         PassReq req; req.step = req.halo = true;
         PassShape s = pass_shape(false, 0, false, req);
-        if (prune_pending && !plan_pass(s).can_step) {      // the outer list's bound stands in for the pruned list's largest tile: if that is all that keeps the pass from integrating, the real figure is needed now
+        if (held.prune_pending() && !plan_pass(s).can_step) {      // the outer list's bound stands in for the pruned list's largest tile: if that is all that keeps the pass from integrating, the real figure is needed now
             s.max_tile_in = 1;
             if (plan_pass(s).can_step) { prune_resolve(true); s = pass_shape(false, 0, false, req); }
         }
@@ -1174,7 +1170,7 @@ template <class T> class Engine final : public EngineBase {
     bool halo_fused_ok(int64_t step_n) {
         if (!(xf_direct && xf.n_peers > 0 && n_ghost > 0 && hp_set && xf.routes) || replan_now) return false;
         if (hp.cm_rows != 3 || hp.n_cm_peers != xf.n_peers || (int)xf.peer_rank.size() != xf.n_peers) return false;
-        if (lp.check_due(step_n, rebuild_every()) && step_n != last_build_step && !(host_prune && inner_valid)) return false;      // (refresh() of such a step only books it)
+        if (lp.check_due(step_n, rebuild_every()) && step_n != last_build_step && !(host_prune && held.inner_valid())) return false;      // (refresh() of such a step only books it)
         return packed_step_possible();
     }
     void halo_fused(int64_t step_n, double dt, bool cm, bool measure) {
@@ -1186,7 +1182,7 @@ template <class T> class Engine final : public EngineBase {
         if (!res.step) throw ApiError{MHIP_ERR_STATE, "internal: the fused ghosted step did not launch"};
         step_parts = res.parts;
         if (cm) step_half ^= 1;
-        halo_cm_in = cm; frc_valid = false; pend_a = nullptr; pending_cm.none();
+        halo_cm_in = cm; drifted();
         hx.trk_step = measure ? step_n + 1 : -1;
         MHIP_HIP(hipGetLastError());
     }
@@ -1211,7 +1207,7 @@ template <class T> class Engine final : public EngineBase {
         inner_is_outer = true; max_tile_in = max_tile; lp.last_prune_step = pass_step;
         ++n_filters; ++n_adopted; gs_list_id = n_filters;
         ghost_flags_in_ok = false; lp.next_check_step = -1; hx.tile_ok = false;
-        inner_valid = true; prune_disp_exceeded = false;
+        held.inner_list_made(Held::Prune::ADOPTED);
         if (debug_on) std::fprintf(stderr, "[mhip] outer list adopted as the inner list (no prune): rows %lld calls %lld\n", (long long)total_rows, (long long)n_force_calls);
     }
 
@@ -1291,10 +1287,10 @@ template <class T> class Engine final : public EngineBase {
         // (with the stage timers on, every job keeps its own launch: a stage's time is then that job's — bench.py's profiling pass, never its timed region)
         req.fuse_spread = gs_ok && small_fused && pme.order >= 4 && pme.order <= 6 && !prof.on;
         req.fuse_terms = gs_ok && !small_fused && !pme.on() && !prof.on;      // (no PME: the bonded terms alone ride with the pair groups)
-        PassRes res = launch_pair_kernel(false, interior_done ? 2 : 0, gs_ok, req);   // (the blocks without ghosts may have run already, while the ghosts were on the wire)
-        interior_done = false;
+        PassRes res = launch_pair_kernel(false, held.interior_done() ? 2 : 0, gs_ok, req);   // (the blocks without ghosts may have run already, while the ghosts were on the wire)
+        held.interior_pass(false);
         bool redo = false;
-        if (prune_disp_exceeded) {   // the outer list could not vouch for this pass: search again and redo it on the fresh list
+        if (held.prune_disp_exceeded()) {   // the outer list could not vouch for this pass: search again and redo it on the fresh list
             after_forces(step_n);
             req.fuse_spread = req.fuse_terms = false;
             if (res.cm_summed) req.cm_sum_in = nullptr;      // (summed by the first pass)
@@ -1324,14 +1320,14 @@ template <class T> class Engine final : public EngineBase {
             prof.begin(6, stream);
             launch_pme_bonded_fused<T>(stream, pme, bonded, G, I, n_owned, cap, pos[cur].p, inv.p, orig[cur].p, frc[cur].p, frc_side.p, res.spread, vp, vp && req.lang);
             prof.end(6, stream);
-            if (vp) { res.step = true; ++n_fused_steps; pend_a = nullptr; frc_valid = false; return res; }
+            if (vp) { res.step = true; ++n_fused_steps; pend_a = nullptr; held.drifted(); return res; }
             pend_a = frc_side.p;
-            frc_valid = true;
+            held.forces_total();
             return res;
         }
         if (bonded.any()) { prof.begin(5, stream); bonded.launch_forces(stream, G, I, pos[cur].p, inv.p, frc[cur].p, orig[cur].p, n_owned, cap, res.terms); prof.end(5, stream); }
         launch_pme_forces();
-        frc_valid = true;
+        held.forces_total();
         return res;
     }
     // frc[cur] += the second force array, for consumers other than the second kick
@@ -1369,11 +1365,15 @@ template <class T> class Engine final : public EngineBase {
         if (ng > 0 && vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites run on a single domain"};
         if (ng > 0 && thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain"};
         n_owned = no; n_ghost = ng; n_tot = no + ng;
-        // new local atom set: restart from the identity order
+        pending_cm.none(); hp_set = false; halo_cm_in = false;
+        new_local_atoms(false);
+    }
+    // a new local atom set (n_owned, n_ghost, n_tot as they now are): restart from the identity order, nothing computed for the old set stands
+    void new_local_atoms(bool in_engine) {
         hipLaunchKernelGGL(k_iota2, dim3(std::min(cdiv(n_tot, 256), 1024)), dim3(256), 0, stream, n_tot, orig[cur].p, inv.p);
         MHIP_HIP(hipMemsetAsync(frc[cur].p, 0, n_tot * sizeof(T4), stream));
         MHIP_HIP(hipGetLastError());
-        stale = true; pending_cm.none(); frc_valid = false; hp_set = false; halo_cm_in = false; trk_issued = false; hx.plan_ok = false; hx.trk_step = -1;
+        held.atoms_replaced(in_engine); hx.plan_ok = false; hx.trk_step = -1;
         // the search radius depends on whether there are ghosts and on the ghost margin, the blocking on the size class: a re-plan
         // that changes neither keeps the grid, its Hilbert table and the (already adapted) capacities
         const int size_class = n_owned >= 100000 ? 2 : (n_owned >= 40000 ? 1 : 0);
@@ -1383,7 +1383,7 @@ template <class T> class Engine final : public EngineBase {
 
     void set_atoms(const void* q, const void* sg, const void* ep, const void* ms, const void* lam, int mem_kind) override {
         flush_cm();
-        frc_run_total = false; frc_before_set_state = false;   // new charges / σ / ϵ / masses: neither a finished run's forces nor those held before a set_state stand
+        held.interactions_changing();
         DBuf<T> s3, s4, s5;
         const T* dq = to_device(q, n_tot, mem_kind, stage_a);
         const T* ds = to_device(sg, n_tot, mem_kind, stage_b);
@@ -1406,13 +1406,12 @@ template <class T> class Engine final : public EngineBase {
             MHIP_HIP(hipStreamSynchronize(stream));
             apply_uniform(h_flags[FLAG_NAN] == 0, h2[0], h2[1]);
         }
-        if (want_eshift() != eshift) stale = true;   // the lists in use are in the other entry format
         pc_valid = false;   // Σq, Σq² of the PME self / net-charge terms are read back only when an energy asks for them
-        params_set = true; frc_valid = false; vs_mass_ok = false;
+        held.params_changed(want_eshift() != eshift); vs_mass_ok = false;
     }
 
     void set_exceptions(const int32_t* ei, const int32_t* ej, int64_t ne, const int32_t* si, const int32_t* sj, int64_t ns) override {
-        frc_run_total = false; frc_before_set_state = false;
+        held.interactions_changing();
         // one CSR over caller indices holding both kinds; excluded beats special (neighbors.jl:410-411 tests eligible first)
         std::vector<std::vector<uint32_t>> adj(cap);
         int span = 0;
@@ -1440,77 +1439,59 @@ template <class T> class Engine final : public EngineBase {
         xl_start.reserve(cap + 1); xl_list.reserve(std::max<size_t>(ls.size(), 1));
         MHIP_HIP(hipMemcpy(xl_start.p, st.data(), (cap + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
         if (!ls.empty()) MHIP_HIP(hipMemcpy(xl_list.p, ls.data(), ls.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        stale = true;   // ≙ cache invalidation after append_excluded_pairs! (test/gpu_consistency.jl:494-527)
+        held.exceptions_changed();
     }
 
     // (new terms change the total force: what a finished run left in frc[cur] is not the next run's first force any more)
-    void set_bonds(int64_t n, const int32_t* i, const int32_t* j, const void* k, const void* r0) override { frc_run_total = false; bonded.set_bonds(cap, n, i, j, (const T*)k, (const T*)r0); }
-    void set_angles(int64_t n, const int32_t* i, const int32_t* j, const int32_t* k, const void* kth, const void* th0) override { frc_run_total = false; bonded.set_angles(cap, n, i, j, k, (const T*)kth, (const T*)th0); }
+    void set_bonds(int64_t n, const int32_t* i, const int32_t* j, const void* k, const void* r0) override { held.terms_changed(); bonded.set_bonds(cap, n, i, j, (const T*)k, (const T*)r0); }
+    void set_angles(int64_t n, const int32_t* i, const int32_t* j, const int32_t* k, const void* kth, const void* th0) override { held.terms_changed(); bonded.set_angles(cap, n, i, j, k, (const T*)kth, (const T*)th0); }
     void set_torsions(int64_t n, const int32_t* i, const int32_t* j, const int32_t* k, const int32_t* l, const int32_t* per, const void* ph, const void* kt) override {
-        frc_run_total = false;
+        held.terms_changed();
         bonded.set_torsions(cap, n, i, j, k, l, per, (const T*)ph, (const T*)kt);
     }
-    void set_ewald_exclusions(int64_t n, const int32_t* i, const int32_t* j) override { frc_run_total = false; bonded.set_ewx(cap, n, i, j); }
+    void set_ewald_exclusions(int64_t n, const int32_t* i, const int32_t* j) override { held.terms_changed(); bonded.set_ewx(cap, n, i, j); }
 
     // set_state raises these words on the device when a coordinate / a velocity really differs from what the engine held
-    DBuf<int32_t> state_changed; bool state_pending = false;
-    bool frc_before_set_state = false;   // were the forces current when the (possibly identical) coordinates came in?
+    DBuf<int32_t> state_changed;
+    void state_write_begins() {
+        state_changed.reserve(2);
+        if (held.state_write_begins()) MHIP_HIP(hipMemsetAsync(state_changed.p, 0, 2 * sizeof(int32_t), stream));
+    }
     void set_state(const void* xyz, const void* v, int mem_kind) override {
         flush_cm();
         const T* dx = to_device(xyz, 3 * (size_t)n_tot, mem_kind, stage_a);
         const T* dv = to_device(v, 3 * (size_t)n_owned, mem_kind, stage_b);
-        state_changed.reserve(2);
-        if (!state_pending) { MHIP_HIP(hipMemsetAsync(state_changed.p, 0, 2 * sizeof(int32_t), stream)); frc_before_set_state = frc_valid; }
-        state_pending = true;
+        state_write_begins();
         hipLaunchKernelGGL(k_scatter_state<T>, dim3(cdiv(n_tot, 256)), dim3(256), 0, stream, n_tot, n_owned, (const int32_t*)inv.p, dx, dv, pos[cur].p, vel[cur].p, G, state_changed.p);
         MHIP_HIP(hipGetLastError());
         if (mem_kind == MHIP_MEM_HOST) MHIP_HIP(hipStreamSynchronize(stream));
-        if (xyz) {
-            // New coordinates, same atoms: the sorted order, the tiles and the pair lists stay (≙ the reference's GPU path, which re-reads
-            // moved coordinates at every call and redoes its sort / tile search only at the step cadence, ext/MollyCUDAExt.jl:774-783).
-            // Whether the lists still cover every cutoff sphere is decided by displacement at the next force call (lists_after_set_state);
-            // lists that have no skin to spend are rebuilt at once, as before.
-            if (!stale && (dual || lazy_single)) coords_moved = true; else stale = true;
-            frc_valid = false; state_set = true; vs_place_due = vs_on;
-        }
+        if (xyz) { held.coords_written(dual || lazy_single); vs_place_due = vs_on; }
     }
 
     // after set_state handed over moved coordinates: keep the lists if nobody outran their margins, else prune / search again
     void lists_after_set_state() {
         bool vel_new = false;
-        if (state_pending) {   // what did set_state really change?  (a state handed back as it was — a run continued in chunks — changes nothing)
-            state_pending = false;
+        if (held.state_pending()) {   // what did set_state really change?
             int32_t h[2] = {1, 1};
             MHIP_HIP(hipMemcpyAsync(h, state_changed.p, sizeof(h), hipMemcpyDeviceToHost, stream));
             MHIP_HIP(hipStreamSynchronize(stream));
-            if (!h[0]) { coords_moved = false; if (frc_before_set_state && !stale) frc_valid = true; }   // the same coordinates again: what was computed for them stands
-            frc_before_set_state = false;
+            held.state_compared(h[0] != 0, h[1] != 0);
             vel_new = h[1] != 0;
-            if (h[0] || h[1]) trk_issued = false;      // a measurement in flight describes the state that was replaced
         }
-        if (vel_new && !stale && (dual || lazy_single) && !coords_moved) {
-            // New velocities on old coordinates (re-thermalisation, a temperature ramp, a replica-exchange swap): the inner skin was
-            // sized for the speeds of the run before.  Look at the new ones now — the drift bound of the checks — instead of at the
-            // next cadence step.
-            vel_check_due = true;
-        }
-        if (!coords_moved) return;
-        coords_moved = false;
-        if (stale) return;
-        vel_check_due = vel_check_due || vel_new;
+        if (!held.moved_coords_taken(vel_new, dual || lazy_single)) return;
         if (dual) {
             const double d_outer = std::sqrt((double)max_disp2_since(pos_snap));
-            if (!lp.prune_stands(d_outer)) { stale = true; return; }
-            if (inner_valid) {
+            if (!lp.prune_stands(d_outer)) { held.lists_voided(); return; }
+            if (held.inner_valid()) {
                 const double d_in = std::sqrt((double)max_disp2_since(pos_snap_in));
-                if (!ListPolicy::covered(d_in, 0.0, lp.skin_in)) inner_valid = false;   // the next force pass re-prunes the outer list
+                if (!ListPolicy::covered(d_in, 0.0, lp.skin_in)) held.prune_wanted();
             }
         } else {   // lazy_single: one list of radius r_list, snapshot of its build in pos_snap_in
             const double d = std::sqrt((double)max_disp2_since(pos_snap_in));
-            if (!ListPolicy::covered(d, 0.0, lp.skin)) stale = true;
-            else if (d > 0) export_needs_search = true;    // fine for forces; mhip_export_neighbors wants the list of the new coordinates
+            if (!ListPolicy::covered(d, 0.0, lp.skin)) held.lists_voided();
+            else if (d > 0) held.export_wants_search();    // fine for forces; mhip_export_neighbors wants the list of the new coordinates
         }
-        if (stale || !inner_valid) ++n_set_state_refresh;
+        if (held.stale() || !held.inner_valid()) ++n_set_state_refresh;
     }
 
     void get_state(void* xyz, void* v, int mem_kind) override {
@@ -1532,16 +1513,16 @@ template <class T> class Engine final : public EngineBase {
         ensure_built(step_n);
         pass_step = step_n;
         launch_pair_kernel(false);
-        frc_valid = false;   // frc holds the pairwise part only
-        if (prune_disp_exceeded) { after_forces(step_n); launch_pair_kernel(false); }
+        held.forces_partial();   // frc holds the pairwise part only
+        if (held.prune_disp_exceeded()) { after_forces(step_n); launch_pair_kernel(false); }
         export_frc(accumulate, f_xyz, mem_kind);
     }
 
     void specific_forces(int accumulate, void* f_xyz, int mem_kind) override {
-        if (!state_set) throw ApiError{MHIP_ERR_STATE, "set_state must be called before specific_forces"};
+        if (!held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_state must be called before specific_forces"};
         MHIP_HIP(hipMemsetAsync(frc[cur].p, 0, (size_t)n_tot * sizeof(T4), stream));
         bonded.launch_forces(stream, G, I, pos[cur].p, inv.p, frc[cur].p, orig[cur].p, n_owned, cap);
-        frc_valid = false;
+        held.forces_partial();
         export_frc(accumulate, f_xyz, mem_kind);
     }
 
@@ -1581,14 +1562,14 @@ template <class T> class Engine final : public EngineBase {
     }
     // Σ over the specific interactions of r ⊗ f (force.jl:991-1060), ADDED to out9
     void specific_virial(double* out9) override {
-        if (!state_set) throw ApiError{MHIP_ERR_STATE, "set_state must be called before specific_virial"};
+        if (!held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_state must be called before specific_virial"};
         const int nb = bonded.launch_virial(stream, G, I, pos[cur].p, inv.p, red_part);
         if (!nb) return;
         for (int c = 0; c < 9; ++c) out9[c] += sum_run((const double*)red_part.p + (size_t)c * nb, nb);
     }
     // reciprocal-space PME virial (recip_conv_inner! ewald.jl:701-723, halved :747-750) + the net-charge term charge_E·I (:925-927), ADDED to out9
     void general_virial(double* out9) override {
-        if (!state_set) throw ApiError{MHIP_ERR_STATE, "set_state must be called before general_virial"};
+        if (!held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_state must be called before general_virial"};
         if (!pme.on()) return;
         const double e = general_potential_energy();           // fills red_part with the 7 component-major runs (and Σq)
         (void)e;
@@ -1601,7 +1582,7 @@ template <class T> class Engine final : public EngineBase {
     }
 
     double specific_potential_energy() override {
-        if (!state_set) throw ApiError{MHIP_ERR_STATE, "set_state must be called before specific_potential_energy"};
+        if (!held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_state must be called before specific_potential_energy"};
         int n_part = bonded.launch_energy(stream, G, I, pos[cur].p, inv.p, red_part);
         if (n_part == 0) return 0.0;
         return read_sum(n_part);
@@ -1624,7 +1605,7 @@ template <class T> class Engine final : public EngineBase {
         tri_mode = approx_images ? 1 : 2;
         ljm = ljm_base;                          // the one-type LJ kernels are cubic-only
         if (pme.on()) pme.setup(pme_order_, pme_mesh_, pme_alpha_, cfg.inter.coul_ke, pme_eps_r_, cfg.box, cfg.periodic, tri_bv);   // (PME set before the boundary: its recip_box again)
-        regrid(); frc_valid = false; state_set = false;
+        regrid(); held.box_changed(false);
     }
     // The boundary of a LIVE context replaced (≙ `sys.boundary = scale_boundary(…)`: scale_coords!, spatial.jl:1184-1218, as the barostats of coupling.jl call it —
     // the reference's force and energy entry points read sys.boundary on every call, ext/MollyCUDAExt.jl:845, 936).  box3: the new side lengths (a TriclinicBoundary:
@@ -1640,8 +1621,7 @@ template <class T> class Engine final : public EngineBase {
             if (std::fabs(bv9[0] - box3[0]) > 1e-12 * bv9[0] || std::fabs(bv9[4] - box3[1]) > 1e-12 * bv9[4] || std::fabs(bv9[8] - box3[2]) > 1e-12 * bv9[8])
                 throw ApiError{MHIP_ERR_INVALID, "set_box: the box must be (v1.x, v2.y, v3.z) of the triclinic basis"};
         }
-        // from here on, whichever way this ends: no list, no forces, the coordinates to be handed over again
-        stale = true; frc_valid = false; frc_run_total = false; frc_before_set_state = false; state_set = false;      // (Σq, Σq² of the PME's constant terms do not depend on the box: pc_valid stays)
+        held.box_changed(true);      // (Σq, Σq² of the PME's constant terms do not depend on the box: pc_valid stays)
         flush_cm();
         MHIP_HIP(hipStreamSynchronize(stream));
         const mhip_config old_cfg = cfg; double old_bv[9]; std::memcpy(old_bv, tri_bv, sizeof(old_bv));
@@ -1662,23 +1642,23 @@ template <class T> class Engine final : public EngineBase {
     int64_t n_box_changes = 0;
     int32_t pme_order_ = 0, pme_mesh_[3] = {0, 0, 0}; double pme_alpha_ = 0, pme_eps_r_ = 1;      // (as last set: a TriclinicBoundary set afterwards rebuilds the reciprocal box)
     void set_pme(int32_t order, const int32_t* mesh, double alpha, double eps_r) override {
-        frc_run_total = false;
+        held.terms_changed();
         MHIP_HIP(hipStreamSynchronize(stream));
         int32_t none[3] = {0, 0, 0};
         pme_order_ = order; pme_alpha_ = alpha; pme_eps_r_ = eps_r; for (int d = 0; d < 3; ++d) pme_mesh_[d] = order ? mesh[d] : 0;
         pme.setup(order, order ? mesh : none, alpha, cfg.inter.coul_ke, eps_r, cfg.box, cfg.periodic, tri_mode ? tri_bv : nullptr);
-        frc_valid = false;
+        held.pme_changed();
     }
     // ≙ AtomsCalculators.forces! of the general interaction (force.jl:792-795): forces added to / written into f_xyz
     void general_forces(int accumulate, void* f_xyz, int mem_kind) override {
-        if (!state_set) throw ApiError{MHIP_ERR_STATE, "set_state must be called before general_forces"};
+        if (!held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_state must be called before general_forces"};
         MHIP_HIP(hipMemsetAsync(frc[cur].p, 0, (size_t)n_tot * sizeof(T4), stream));
         launch_pme_forces();
-        frc_valid = false;
+        held.forces_partial();
         export_frc(accumulate, f_xyz, mem_kind);
     }
     double general_potential_energy() override {
-        if (!state_set) throw ApiError{MHIP_ERR_STATE, "set_state must be called before general_potential_energy"};
+        if (!held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_state must be called before general_potential_energy"};
         if (!pme.on()) return 0.0;
         if (n_ghost > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "PME runs on a single domain"};
         if (!pc_valid) {   // Σq and Σq² (ewald.jl:917-924) from the charges kept in pos.w
@@ -1759,17 +1739,16 @@ template <class T> class Engine final : public EngineBase {
     // that had no side arrays pending).  A run that continues from exactly that state — the chunked simulate! of test/simulation.jl:16-57,
     // a benchmark's consecutive windows — finds the forces of its first step already there: the reference recomputes them
     // (simulators.jl:564-571), which yields the same numbers from the same lists in the same order.
-    bool frc_run_total = false;
     const bool reuse_run_forces = env_int("MOLLYHIP_REUSE_RUN_FORCES", 1) != 0;
     int64_t n_reused_starts = 0;
     void vv_init(int64_t first_step) override {
-        if (!state_set) throw ApiError{MHIP_ERR_STATE, "set_state must be called before vv_run"};
+        if (!held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_state must be called before vv_run"};
         lists_after_set_state();           // (a set_state that brought the SAME coordinates leaves the forces valid)
-        const bool had = frc_run_total && frc_valid && reuse_run_forces && !stale && !coords_moved;
-        const int64_t reb0 = n_outer, fil0 = n_filters; const bool inner0 = inner_valid;   // (searches re-sort, prunes change the list walked)
-        frc_run_total = false;
+        const bool had = held.reusable_run_forces() && reuse_run_forces;
+        const int64_t reb0 = n_outer, fil0 = n_filters; const bool inner0 = held.inner_valid();   // (searches re-sort, prunes change the list walked)
+        held.run_begins();
         start_lists(first_step);
-        if (had && n_outer == reb0 && n_filters == fil0 && inner_valid == inner0 && (inner_valid || !dual) && !prune_disp_exceeded) { ++n_reused_starts; return; }
+        if (had && n_outer == reb0 && n_filters == fil0 && held.inner_valid() == inner0 && (held.inner_valid() || !dual) && !held.prune_disp_exceeded()) { ++n_reused_starts; return; }
         step_forces(first_step);
         fold_side_forces();
     }
@@ -1777,7 +1756,7 @@ template <class T> class Engine final : public EngineBase {
         if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no constraints: use mhip_vv_run"};
         if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no virtual sites: use mhip_vv_run"};
         if (thermo_on() && !in_run) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no rescaling thermostat: use mhip_vv_run"};
-        if (!frc_valid) throw ApiError{MHIP_ERR_STATE, "vv_stage1 needs forces from vv_init / vv_stage2"};
+        if (!held.frc_valid()) throw ApiError{MHIP_ERR_STATE, "vv_stage1 needs forces from vv_init / vv_stage2"};
         lp.cur_dt = dt;
         tr("k_vv1");
         prof.begin(2, stream);
@@ -1836,7 +1815,7 @@ template <class T> class Engine final : public EngineBase {
 
     void set_ghost_margin(double m) override {
         if (!(m >= 0) || std::isinf(m)) throw ApiError{MHIP_ERR_INVALID, "ghost margin must be finite and >= 0"};
-        ghost_margin = m; stale = true; host_prune = m > 0;
+        ghost_margin = m; held.lists_voided(); host_prune = m > 0;
         if (n_ghost > 0) { setup_grid(); choose_blocking(); }
     }
     // max |x − x_plan|² over owned and ghost atoms since the outer search of the current ghost plan, as a float in device memory
@@ -1846,28 +1825,28 @@ template <class T> class Engine final : public EngineBase {
     // sub-domain has to be re-planned at every rebuild step anyway.
     void plan_disp2_dev(float* out_dev) override {
         const uint32_t inf_bits = 0x7f800000u;
-        if (!dual || stale) { MHIP_HIP(hipMemsetD32Async((hipDeviceptr_t)out_dev, (int)inf_bits, 2, stream)); return; }
+        if (!dual || held.stale()) { MHIP_HIP(hipMemsetD32Async((hipDeviceptr_t)out_dev, (int)inf_bits, 2, stream)); return; }
         MHIP_HIP(hipMemsetAsync(out_dev, 0, 2 * sizeof(float), stream));
         const dim3 g(std::min(cdiv(n_tot, 256), 1024));
         hipLaunchKernelGGL(k_max_disp<T>, g, dim3(256), 0, stream, n_tot, (const T4*)pos[cur].p, (const T4*)pos_snap.p, reinterpret_cast<unsigned int*>(out_dev), G);
-        if (inner_valid) hipLaunchKernelGGL(k_max_disp<T>, g, dim3(256), 0, stream, n_tot, (const T4*)pos[cur].p, (const T4*)pos_snap_in.p, reinterpret_cast<unsigned int*>(out_dev) + 1, G);
+        if (held.inner_valid()) hipLaunchKernelGGL(k_max_disp<T>, g, dim3(256), 0, stream, n_tot, (const T4*)pos[cur].p, (const T4*)pos_snap_in.p, reinterpret_cast<unsigned int*>(out_dev) + 1, G);
         else MHIP_HIP(hipMemsetD32Async((hipDeviceptr_t)(out_dev + 1), (int)inf_bits, 1, stream));
         MHIP_HIP(hipGetLastError());
     }
-    void request_prune() override { inner_valid = false; }
+    void request_prune() override { held.prune_wanted(); }
     // {max |x − x_plan|², max |x − x_prune|², max |v|² of the owned atoms} as floats in device memory, ready for ONE MAX all-reduce over
     // the ranks; mhip_plan_decide takes the reduced triple.  +inf in [0]: this sub-domain is re-planned at every rebuild step anyway.
     void plan_state_dev(float* out_dev) override {
         const uint32_t inf_bits = 0x7f800000u;
         MHIP_HIP(hipMemsetAsync(out_dev, 0, 3 * sizeof(float), stream));
-        if (!dual || stale) { MHIP_HIP(hipMemsetD32Async((hipDeviceptr_t)out_dev, (int)inf_bits, 2, stream)); return; }
+        if (!dual || held.stale()) { MHIP_HIP(hipMemsetD32Async((hipDeviceptr_t)out_dev, (int)inf_bits, 2, stream)); return; }
         const dim3 g(std::min(cdiv(n_owned, 1024), 512));
         unsigned int* w = reinterpret_cast<unsigned int*>(out_dev);
         // owned atoms only: every ghost is an owned atom of some rank, and the MAX runs over all of them (the call may come before
         // this step's ghost coordinates are in)
         hipLaunchKernelGGL(k_max_disp<T>, g, dim3(1024), 0, stream, n_owned, (const T4*)pos[cur].p, (const T4*)pos_snap.p, w, G, (const T4*)vel[cur].p, n_owned, w + 2,
-                           inner_valid ? (const T4*)pos_snap_in.p : (const T4*)nullptr, inner_valid ? w + 1 : (unsigned int*)nullptr);
-        if (!inner_valid) MHIP_HIP(hipMemsetD32Async((hipDeviceptr_t)(out_dev + 1), (int)inf_bits, 1, stream));
+                           held.inner_valid() ? (const T4*)pos_snap_in.p : (const T4*)nullptr, held.inner_valid() ? w + 1 : (unsigned int*)nullptr);
+        if (!held.inner_valid()) MHIP_HIP(hipMemsetD32Async((hipDeviceptr_t)(out_dev + 1), (int)inf_bits, 1, stream));
         MHIP_HIP(hipGetLastError());
     }
     // The collective decision at the rebuild cadence, made by every rank from the same reduced numbers with the criteria of the
@@ -1884,18 +1863,18 @@ template <class T> class Engine final : public EngineBase {
             lp.start_inner_skin(true, inner_skin_floor(), false);
             set_prune_radius();
         }
-        if (!dual || stale || std::isinf(red3[0])) return 2;
+        if (!dual || held.stale() || std::isinf(red3[0])) return 2;
         lp.measured(std::sqrt((double)red3[2]));
         // (measured at step_n, applied `late` steps later; the list is walked up to the pass of step_n + every — the next check's own step — as in resolve_track;
         // not good for a whole interval, but for k steps: the host looks again then, it owns the step loop; a prune runs inside the NEXT force pass, one step
         // from now (+ late): the outer test leaves it that much headroom)
-        const ListPolicy::Measured m{inner_valid ? std::sqrt((double)red3[1]) : (double)INFINITY, std::sqrt((double)red3[0]), step_n - lp.last_prune_step};
+        const ListPolicy::Measured m{held.inner_valid() ? std::sqrt((double)red3[1]) : (double)INFINITY, std::sqrt((double)red3[0]), step_n - lp.last_prune_step};
         const ListPolicy::Decision r = lp.decide(m, ListPolicy::Applied::collective(rebuild_every(), step_n, late, check_in != nullptr, n_ghost > 0));
         if (r.grown) inner_skin_grown(r.ahead);
         switch (r.action) {
         case ListPolicy::KEEP: return 0;
         case ListPolicy::LOOK_AGAIN: *check_in = r.k; return 0;
-        case ListPolicy::PRUNE: inner_valid = false; return 1;
+        case ListPolicy::PRUNE: held.prune_wanted(); return 1;
         default: return 2;
         }
     }
@@ -1977,13 +1956,12 @@ template <class T> class Engine final : public EngineBase {
         tr("k_vv_mid");
         vv_mid_launch(cm, last, nb, dt, cm_in, n_in, cm_out, false);
         prof.end(2, stream);
-        pend_a = nullptr; pending_cm.none();
+        step_closed(!last);
         if (due && !dual) refresh(step_n);
         if (!last) {
             pending_cm.n = nb;
             if (solo) cm_half ^= 1; else halo_pack(cm);
             halo_cm_in = cm;
-            frc_valid = false;                                                    // frc[cur] belongs to the coordinates before the drift
         } else halo_cm_in = false;
         MHIP_HIP(hipGetLastError());
     }
@@ -2124,7 +2102,7 @@ template <class T> class Engine final : public EngineBase {
     }
     // the collective validity check of the pair lists, issued at step s and read one step later (nothing waits for it)
     void xf_issue_plan_check(int64_t s) {
-        if (hx.trk_step == s && dual && inner_valid && !stale) {      // measured by the fused launch that made these coordinates (per-block maxima, kernels.h STEP epilogue)
+        if (hx.trk_step == s && dual && held.inner_list_stands()) {      // measured by the fused launch that made these coordinates (per-block maxima, kernels.h STEP epilogue)
             hipLaunchKernelGGL(k_track_reduce, dim3(1), dim3(256), 0, stream, step_parts, (const float*)trk_part.p, xf.mine3.p, (float*)nullptr, 1);
             MHIP_HIP(hipGetLastError());
         } else plan_state_dev(xf.mine3.p);
@@ -2161,7 +2139,7 @@ template <class T> class Engine final : public EngineBase {
                 host_prune = false; engine_sched = true;
                 lp.start_inner_skin(true, inner_skin_floor());
                 set_prune_radius();
-                inner_valid = false;
+                held.prune_wanted();
             }
             lp.cur_dt = dt;
             const int64_t c0 = lp.n_disp_checks, f0 = n_filters, o0 = n_outer;
@@ -2170,7 +2148,7 @@ template <class T> class Engine final : public EngineBase {
             flush_cm();
             *steps_done = n_steps;
             // (checks: those read so far + the one a launch has measured and the next call's first step will read)
-            if (counters) { counters[0] += lp.n_disp_checks - c0 + (trk_issued ? 1 : 0); counters[1] += n_filters - f0; counters[2] += n_outer - o0; }
+            if (counters) { counters[0] += lp.n_disp_checks - c0 + (held.trk_issued() ? 1 : 0); counters[1] += n_filters - f0; counters[2] += n_outer - o0; }
             dom.n_replans += n_outer - o0;
             MHIP_HIP(hipGetLastError());
             MHIP_HIP(hipStreamSynchronize(stream));
@@ -2219,7 +2197,7 @@ template <class T> class Engine final : public EngineBase {
                 ++*steps_done;
                 continue;
             }
-            if (debug_on) std::fprintf(stderr, "[mhip %d] %.3f step %lld separate launches (reads exchange %u) replan %d stop %d inner_valid %d\n", xf.rank, now_ms(), (long long)s, xf.seq, (int)replan_here, (int)stop, (int)inner_valid);
+            if (debug_on) std::fprintf(stderr, "[mhip %d] %.3f step %lld separate launches (reads exchange %u) replan %d stop %d inner_valid %d\n", xf.rank, now_ms(), (long long)s, xf.seq, (int)replan_here, (int)stop, (int)held.inner_valid());
             if (n_ghost > 0 && xf.n_peers > 0 && !replan_here) (void)halo_interior(s);          // the blocks that need no ghost, while the peers' rows arrive
             halo_mid(s, dt, (cm ? 1 : 0) | (stop ? 2 : 0), (cm && stop) ? cm_parts_dev : nullptr, (cm && stop) ? n_parts : 0);   // waits + unpacks … packs + sends
             ++*steps_done;
@@ -2411,19 +2389,14 @@ template <class T> class Engine final : public EngineBase {
         // commit: the new local set in its identity order
         cur = n; dom.gcur = gn; dom.n_migrated += t.n_arrive;
         n_owned = t.n_owned; n_ghost = t.n_ghost; n_tot = n_owned + n_ghost;
-        hipLaunchKernelGGL(k_iota2, dim3(std::min(cdiv(n_tot, 256), 1024)), dim3(256), 0, stream, n_tot, orig[cur].p, inv.p);
-        MHIP_HIP(hipMemsetAsync(frc[cur].p, 0, n_tot * sizeof(T4), stream));
-        stale = true; frc_valid = false; trk_issued = false; interior_done = false; frc_run_total = false; coords_moved = false; state_pending = false;
-        const int size_class = n_owned >= 100000 ? 2 : (n_owned >= 40000 ? 1 : 0);
-        const long long key = (n_ghost > 0 ? 1 : 0) | (dual_disabled ? 2 : 0) | (size_class << 2) | (margin_halvings << 4) | (margin_zero ? 128 : 0) | ((long long)std::llround(ghost_margin * 1e6) << 8);
-        if (key != grid_key) { setup_grid(); choose_blocking(); grid_key = key; }
+        new_local_atoms(true);
         const bool all_equal = t.uni_bad == 0;
         if ((ljm == LJ_DIST_UNIFORM) != (ljm_base == LJ_DIST && all_equal && dom.h_lj0[0] != T(0) && dom.h_lj0[1] != T(0)) || dom.h_lj0[0] != uni_s0 || dom.h_lj0[1] != uni_e0) apply_uniform(all_equal, dom.h_lj0[0], dom.h_lj0[1]);
         // the per-step message of the new plan (mhip_halo_plan, mhip_halo_routes): tables made by the kernels above
         hp.first_ghost = n_owned; hp.n_recv_rows = t.n_ghost + (world - 1) * cr; hp.recv = nullptr; hp.recv_dst = dom.recv_dst.p;
         hp.n_cm_peers = world - 1; hp.cm_rows = cr; hp.send_idx = dom.send_idx.p; hp.send_shift = dom.send_shift.p;
         hp.n_send_rows = t.n_send + (world - 1) * cr; hp.send = nullptr; hp.send_cm_pos = dom.send_cm_pos.p; hp.n_send_cm = (world - 1) * cr;
-        xf.plan_pending = false; xf.next_check = -1; hx.plan_ok = false; hx.trk_step = -1;
+        xf.plan_pending = false; xf.next_check = -1;
         dom.plan_ms += ms_since(t_begin);
         const auto t_search = std::chrono::steady_clock::now();
         rebuild(step_n);
@@ -2440,13 +2413,12 @@ template <class T> class Engine final : public EngineBase {
     // Only on steps whose force pass is a plain one over lists that are known to be good (no search, no prune, no cadence decision
     // pending); returns 1 if it launched, 0 if halo_end will do the whole pass.
     int halo_interior(int64_t step_n) override {
-        interior_done = false;
-        if (n_ghost == 0 || stale || !frc_valid_for_split() || (step_n % rebuild_every() == 0 && step_n != last_build_step)) return 0;
+        held.interior_pass(false);
+        if (n_ghost == 0 || held.stale() || !held.split_pass_ok(dual, lazy_single) || (step_n % rebuild_every() == 0 && step_n != last_build_step)) return 0;
         launch_pair_kernel(false, 1);
-        interior_done = true;
+        held.interior_pass(true);
         return 1;
     }
-    bool frc_valid_for_split() const { return dual ? inner_valid : !lazy_single; }
     void halo_end(int64_t step_n, double dt, int64_t first, int64_t n, const void* in_dev, double* cm_out4_dev) override {
         if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain, stepped by mhip_vv_run"};
         scatter_coords(first, n, in_dev);
@@ -2457,13 +2429,16 @@ template <class T> class Engine final : public EngineBase {
         }
         MHIP_HIP(hipGetLastError());
     }
-    void rebuild_now(int64_t step_n) override { flush_cm(); resolve_track(step_n); lists_after_set_state(); if (stale) rebuild(step_n); else refresh(step_n); }
+    void rebuild_now(int64_t step_n) override { flush_cm(); resolve_track(step_n); lists_after_set_state(); if (held.stale()) rebuild(step_n); else refresh(step_n); }
 
+    // an integrator launch has consumed the side array and the pending Σ m v removal; moved_on: it also moved the coordinates on, frc[cur] belongs to those before the drift
+    void step_closed(bool moved_on) { pend_a = nullptr; pending_cm.none(); if (moved_on) held.drifted(); }
+    void drifted() { step_closed(true); }
     // the tail of a step whose force pass integrated (res.step, of vv_loop and langevin_run): the check it measured is issued for trk_at, the Σ m v
     // partials it left in cm_blk are pending removal, frc[cur] belongs to the coordinates before the drift
     void after_fused_step(const PassRes& res, bool measure, int64_t trk_at, bool cm) {
         if (measure) issue_track(res.parts, trk_at);
-        pend_a = nullptr; pending_cm.none(); frc_valid = false;
+        drifted();
         if (cm) { pending_cm.resum(cm_blk.p + (size_t)step_half * 4 * res.parts, res.parts); step_half ^= 1; }
     }
     // one k_vv_mid launch of nb blocks (last: the closing kick alone); measure: the maxima of the next step's check into trk_part
@@ -2478,7 +2453,7 @@ template <class T> class Engine final : public EngineBase {
     }
 
     void vv_run(int64_t first_step, int64_t n_steps, double dt, int remove_cm_every) override {
-        if (!state_set || !params_set) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before vv_run"};
+        if (!held.state_set() || !held.params_set()) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before vv_run"};
         if (n_ghost > 0) throw ApiError{MHIP_ERR_STATE, "vv_run is single-domain; drive ghosted domains with vv_stage1/vv_stage2"};
         lp.cur_dt = dt;
         InRun guard_in_run(in_run);
@@ -2515,7 +2490,7 @@ template <class T> class Engine final : public EngineBase {
                 prof.begin(2, stream);
                 con_launch(0, con_blocks(), dt, nullptr, false, nullptr);
                 prof.end(2, stream);
-                pending_cm.none(); frc_valid = false;
+                drifted();
             } else vv_stage1(dt);
         }
         for (int64_t step = first_step + 1; step <= last; ++step) {
@@ -2523,7 +2498,7 @@ template <class T> class Engine final : public EngineBase {
             // find_neighbors at step % n_steps == 0 (:645, neighbors.jl:396) builds the list from the coordinates of THIS step; it is
             // scheduled before the force pass so that, with the dual pair list, that pass can prune the outer list on the way.
             // Forces are unaffected: the pass walks a superset of the old list and every interaction has a cutoff <= r_list.
-            if (trk_issued && step > trk_step) resolve_track(step);
+            if (held.trk_issued() && step > trk_step) resolve_track(step);
             if (pre && lp.check_due(step, every)) refresh(step);
             const bool cm = remove_cm_every != 0 && step % remove_cm_every == 0;
             const bool th = thermo_on() && step % thermo.n_steps == 0;            // :630, behind this step's CM removal
@@ -2534,7 +2509,7 @@ template <class T> class Engine final : public EngineBase {
                 continue;
             }
             // the validity check of step + 1 is measured where its coordinates are made: by this step's integrator launch — or by the pair pass itself when it integrates
-            const bool measure = step != last && async_ok() && !trk_issued && lp.check_due(step + 1, every);
+            const bool measure = step != last && async_ok() && !held.trk_issued() && lp.check_due(step + 1, every);
             const bool integrate = step != last && !items_on() && !th;            // (λ needs Σ m v² of ALL atoms between the kicks: no force launch integrates on such a step)
             PassReq req;
             req.step = integrate && !bonded.any() && !pme.on(); req.cm = cm;      // (one kernel either way: its stage time is its own, so the stage timers leave it fused)
@@ -2554,17 +2529,16 @@ template <class T> class Engine final : public EngineBase {
             double* cm_out = cm ? (parts_out ? cm_parts_last : cm_step.p + (size_t)half * 4 * 1024) : (double*)nullptr;
             prof.begin(2, stream);
             // the speeds for a check that the next step's force pass will measure (see resolve_track); evaluated behind the pass: a prune inside it makes the lists checkable again
-            const bool measure_mid = step != last && async_ok() && !trk_issued && lp.check_due(step + 1, every);
+            const bool measure_mid = step != last && async_ok() && !held.trk_issued() && lp.check_due(step + 1, every);
             if (measure_mid) trk_reserve(n_blocks);
             if (th) thermo_step(step, step == last, nb, dt, cm_out, measure_mid);
             else if (items_on()) con_launch(step == last ? 2 : 1, nb, dt, cm_out, measure_mid, nullptr);
             else vv_mid_launch(cm, step == last, nb, dt, pending_cm.parts_arg(), pending_cm.n, cm_out, measure_mid);
             prof.end(2, stream);
             if (measure_mid) issue_track(nb, step + 1);   // the check of step + 1, read by resolve_track at step + 2
-            if (step == last) frc_run_total = pend_a == nullptr && n_ghost == 0;   // (side arrays are added by the kick, not folded)
-            pend_a = nullptr; pending_cm.none();
+            if (step == last) held.run_ended(pend_a == nullptr && n_ghost == 0);
+            step_closed(step != last);
             if (cm && !parts_out && !th) { pending_cm.resum(cm_out, nb); half ^= 1; }      // (th: removed with the scale, nothing is pending)
-            if (step != last) frc_valid = false;                                  // frc[cur] belongs to the coordinates before the drift
         }
     }
 
@@ -2687,28 +2661,25 @@ template <class T> class Engine final : public EngineBase {
         MHIP_HIP(hipMemcpy(vs_rec.p, rec.data(), rec.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         MHIP_HIP(hipMemcpy(vs_w.p, vs.w.data(), vs.w.size() * sizeof(double), hipMemcpyHostToDevice));
         MHIP_HIP(hipMemcpy(vs_flag.p, vs.flag.data(), vs.flag.size(), hipMemcpyHostToDevice));
-        sites = std::move(vs); vs_on = true; vs_place_due = state_set; vs_mass_ok = false; frc_run_total = false;
+        sites = std::move(vs); vs_on = true; vs_place_due = held.state_set(); vs_mass_ok = false; held.terms_changed();
     }
     VsP<T> vs_params() const { VsP<T> V{}; V.n = sites.n; V.rec = vs_rec.p; V.w = vs_w.p; V.inv = inv.p; return V; }
     // place_virtual_sites! on the coordinates the context holds.  To the lists and the forces this is a set_state of the sites' rows: the same protocol
     // (a site that already sat where its parents put it changes nothing, so a run continued in chunks finds its forces and lists as it left them)
     void place_virtual_sites() override {
-        if (!state_set) throw ApiError{MHIP_ERR_STATE, "set_state must be called before place_virtual_sites"};
+        if (!held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_state must be called before place_virtual_sites"};
         vs_place_due = false;
         if (!vs_on) return;
-        state_changed.reserve(2);
-        if (!state_pending) { MHIP_HIP(hipMemsetAsync(state_changed.p, 0, 2 * sizeof(int32_t), stream)); frc_before_set_state = frc_valid; }
-        state_pending = true;
+        state_write_begins();
         tr("k_vs_place");
         launch_vs_place<T>(stream, vs_params(), pos[cur].p, G, state_changed.p);
         MHIP_HIP(hipGetLastError());
-        if (!stale && (dual || lazy_single)) coords_moved = true; else stale = true;
-        frc_valid = false;
+        held.coords_written(dual || lazy_single);
     }
     // distribute_forces! in place on the caller's packed xyz array (caller order); r12, r13 of an OutOfPlaneSite from the context's coordinates
     void distribute_forces(void* f_xyz, int mem_kind) override {
         if (!vs_on) return;
-        if (!state_set && sites.n_type[3] > 0) throw ApiError{MHIP_ERR_STATE, "set_state must be called before distribute_forces (OutOfPlaneSite)"};
+        if (!held.state_set() && sites.n_type[3] > 0) throw ApiError{MHIP_ERR_STATE, "set_state must be called before distribute_forces (OutOfPlaneSite)"};
         T* d = (T*)f_xyz;
         const size_t count = 3 * (size_t)cfg.n_atoms;
         if (mem_kind == MHIP_MEM_HOST) { stage_a.reserve(count); d = stage_a.p; MHIP_HIP(hipMemcpyAsync(d, f_xyz, count * sizeof(T), hipMemcpyHostToDevice, stream)); }
@@ -2726,7 +2697,7 @@ template <class T> class Engine final : public EngineBase {
     // placed if coordinates came in since they last were (simulators.jl:561-562, 1113-1114)
     void sites_run_start() {
         if (!vs_on) return;
-        if (!state_set || !params_set) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before a run"};
+        if (!held.state_set() || !held.params_set()) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before a run"};
         if (andersen_prob > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen thermostat with virtual sites is not supported"};
         if (con.first_unhosted >= 0)
             throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual site " + std::to_string(con.first_unhosted) + " (atom " + std::to_string(sites.site[con.first_unhosted]) +
@@ -2781,7 +2752,7 @@ template <class T> class Engine final : public EngineBase {
     // mode 0: one application of the Andersen thermostat with per-atom probability `prob` (coupling.jl:196-211);
     // mode 1: random_velocities! (spatial.jl:803-831).  Velocities only: positions, forces and the pair list stay valid.
     void redraw_velocities(int mode, double kT, double prob, uint64_t key, uint64_t ctr1) override {
-        if (!state_set || !params_set) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before drawing velocities"};
+        if (!held.state_set() || !held.params_set()) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before drawing velocities"};
         if (n_ghost > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "velocity draws are single-domain"};
         if (!(kT >= 0)) throw ApiError{MHIP_ERR_INVALID, "kT must be non-negative"};
         StochP<T> P = stoch_params(kT, key, ctr1);
@@ -2810,7 +2781,7 @@ template <class T> class Engine final : public EngineBase {
     // coordinates, ONE fused update launch (kick, half drift, O-step, half drift, wrap, Σ m v partials), the neighbour cadence.
     // ctr1 advances by one per step (:1190) from ctr1_0 + (first_step's offset), so chunked continuation reproduces one long run.
     void langevin_run(int64_t first_step, int64_t n_steps, double dt, double kT, double friction, int remove_cm_every, uint64_t key, uint64_t ctr1_0) override {
-        if (!state_set || !params_set) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before langevin_run"};
+        if (!held.state_set() || !held.params_set()) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before langevin_run"};
         if (n_ghost > 0) throw ApiError{MHIP_ERR_STATE, "langevin_run is single-domain"};
         if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats are a coupling of mhip_vv_run: unset the thermostat before mhip_langevin_run"};
         if (!(kT >= 0) || !(friction >= 0)) throw ApiError{MHIP_ERR_INVALID, "temperature and friction must be non-negative"};
@@ -2832,12 +2803,12 @@ template <class T> class Engine final : public EngineBase {
         for (int64_t step = first_step + 1; step <= first_step + n_steps; ++step) {
             // a check measured by the update launch of step s (the coordinates x_s it made) is read at the top of step s + 2, behind a whole step of queued work — the
             // scheme of mhip_vv_run, whose loop is one force pass ahead of this one (there the launch of step s makes x_(s+1)); a check left by a run before: at once
-            if (trk_issued && (!in_lang_async || step > trk_step + 1)) resolve_track(step);
+            if (held.trk_issued() && (!in_lang_async || step > trk_step + 1)) resolve_track(step);
             const bool cm = remove_cm_every != 0 && step % remove_cm_every == 0;
             P.ctr1 = ctr1_0 + (uint64_t)(step - first_step - 1);
             // a small system's step (bonded terms + PME): its last force launch — interpolation + bonded sums — runs the update as well (step_fused.h, k_gather_collect_vv<…, LANG>),
             // every step of the run: a Langevin step is complete in itself, there is no closing half kick to keep a launch for
-            const bool measure = in_lang_async && async_ok() && !trk_issued && lp.check_due(step, every);      // the check refresh(step) below would make with a drained stream
+            const bool measure = in_lang_async && async_ok() && !held.trk_issued() && lp.check_due(step, every);      // the check refresh(step) below would make with a drained stream
             PassReq req;
             req.gcv = bonded.any() && pme.on() && !items; req.step = !bonded.any() && !pme.on() && !items; req.lang = &P; req.cm = cm; req.measure = measure; req.dt = dt;      // (step: the packed fp32 one-type pass runs the update in its epilogue, k_forces<…, STEP, ·, LANG>)
             const PassRes res = step_forces(step, req);                          // :1173
@@ -2858,7 +2829,7 @@ template <class T> class Engine final : public EngineBase {
                                pending_cm.vcm_arg(vcm.p), pending_cm.parts_arg(), pending_cm.n,
                                cm_out, G, (const T4*)pend_a);      // (the side array of a small system's step is added by the update itself, as k_vv_mid does: no k_add_forces launch)
             prof.end(2, stream);
-            pend_a = nullptr; pending_cm.none(); frc_valid = false;
+            drifted();
             if (cm) { pending_cm.resum(cm_out, nb); half ^= 1; }   // :1204-1206, subtracted by the next consumer
             apply_coupling(step);                                                 // :1208
             if (lp.check_due(step, every)) refresh(step);                            // :1211 — the next force pass prunes the fresh outer list
@@ -2874,12 +2845,12 @@ template <class T> class Engine final : public EngineBase {
     // now = false (statistics): count the pairs of the list in use, never search for it
     int64_t export_list(int32_t* oi, int32_t* oj, uint8_t* osp, int64_t capacity, bool now) {
         if (now) lists_after_set_state();
-        if (stale) {   // never built, or invalidated by new coordinates / exceptions: search now
+        if (held.stale()) {   // never built, or invalidated by new coordinates / exceptions: search now
             if (!now) return 0;
-            if (!state_set || !params_set) throw ApiError{MHIP_ERR_STATE, "no neighbour list: call set_atoms and set_state first"};
+            if (!held.state_set() || !held.params_set()) throw ApiError{MHIP_ERR_STATE, "no neighbour list: call set_atoms and set_state first"};
             flush_cm(); rebuild(last_build_step == std::numeric_limits<int64_t>::min() ? 0 : last_build_step);
         }
-        if (now && lazy_single && (last_build_step != lp.last_prune_step || export_needs_search)) { flush_cm(); rebuild(last_build_step); }   // skipped rebuilds / moved coordinates: hand out the list of NOW
+        if (now && lazy_single && (last_build_step != lp.last_prune_step || held.export_needs_search())) { flush_cm(); rebuild(last_build_step); }   // skipped rebuilds / moved coordinates: hand out the list of NOW
         const int32_t *x_tidx = tile_idx.p, *x_tcnt = tile_cnt.p, *x_rows = wave_rows.p; const uint2* x_nbr = nbr.p;
         if (dual) {
             // the reference's list at the current coordinates = the outer list filtered with the exact predicate; valid as long as
@@ -2932,11 +2903,11 @@ template <class T> class Engine final : public EngineBase {
         s->n_group_split_passes = n_gs_passes; s->group_split = gs_groups(); s->n_adopted_outer_lists = (int32_t)std::min<int64_t>(n_adopted, INT32_MAX);
         s->n_fused_steps = n_fused_steps; s->n_box_changes = n_box_changes; s->pme_fft = pme.on() && pme.fft ? 1 : 0;
         s->n_list_slots = total_rows * 4 * WAVE;
-        if (!stale) {
+        if (!held.stale()) {
             std::vector<int32_t> tc(n_blocks);
             MHIP_HIP(hipMemcpy(tc.data(), tile_cnt.p, n_blocks * sizeof(int32_t), hipMemcpyDeviceToHost));
             int64_t t = 0; for (int v : tc) t += v; s->tile_atoms_total = s->outer_tile_atoms_total = t;
-            if (dual && inner_valid && !inner_is_outer && tile_cnt_in.p) {      // the plain passes stage the pruned list's compacted tile
+            if (dual && held.inner_valid() && !inner_is_outer && tile_cnt_in.p) {      // the plain passes stage the pruned list's compacted tile
                 MHIP_HIP(hipMemcpy(tc.data(), tile_cnt_in.p, n_blocks * sizeof(int32_t), hipMemcpyDeviceToHost));
                 t = 0; for (int v : tc) t += v; s->tile_atoms_total = t;
             }
