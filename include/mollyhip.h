@@ -149,6 +149,7 @@ typedef struct mhip_stats {
     /* HIP-event timings, filled while profiling is on (mhip_set_profiling):                        */
     /* stage 0 pair-force kernel, 1 tile/list build kernel (outer search), 2 integrator kernels,    */
     /* 3 sort+permute, 4 force passes that prune the outer list, 5 bonded kernels, 6 PME reciprocal */
+    /* space, 7 the constraint-virial kernel of mhip_constraint_virial                              */
     double  prof_ms[8];
     int64_t prof_calls[8];
     int64_t n_outer_builds;        /* searches with the outer radius (dual pair list)             */
@@ -325,14 +326,28 @@ int32_t mhip_philox4x32_10(const uint32_t* ctr4, const uint32_t* key2, uint32_t*
  * plan, a TriclinicBoundary, or the Andersen coupling (mhip_set_andersen, prob > 0); the split step (mhip_vv_init / stage1 / stage2) and the halo
  * paths refuse a constrained context.  mhip_vv_run and mhip_langevin_run then apply RATTLE after every kick and SHAKE (with the velocity correction
  * v += Δx/dt) after every drift, in the reference's order (simulators.jl:589-620, 1155-1185).  The virials (virial9 of mhip_forces, mhip_*_virial)
- * stay the force virials: they leave out the constraint contribution (shake.jl:205-470).  The solves run in double precision; RATTLE is one exact
- * linear solve per cluster, so vel_tol is only checked to be positive. */
+ * stay the force virials: they leave out the constraint contribution (shake.jl:205-470), which mhip_constraint_virial computes on request for the
+ * state held.  The solves run in double precision; RATTLE is one exact linear solve per cluster, so vel_tol is only checked to be positive. */
 int32_t mhip_set_constraints(mhip_ctx* ctx, int64_t n_dist, const int32_t* i, const int32_t* j, const double* dist,
                              int64_t n_angle, const int32_t* ai, const int32_t* aj, const int32_t* ak, const double* d3,
                              double dist_tol, double vel_tol, int32_t max_iters);
 /* out[8]: clusters of 2 / 3 / 4 atoms and angle clusters; constraints (degrees of freedom removed); the most SHAKE iterations any cluster took
  * in the last run; the count of cluster-solves that stopped at max_iters since set; spare */
 int32_t mhip_constraint_info(mhip_ctx* ctx, int64_t* out8);
+/* constraint contribution to the virial at the context's coordinates and velocities, by the reference's trial step
+ * (merge_initial_constraint_virial!, simulators.jl:459-495; shake.jl:234-392): v <- RATTLE(x, v); v1 = v + (f/m) dt, v2 = RATTLE(x, v1),
+ * Wv = (1/dt) sum_clusters lambda_c sum_k loc_k (x) m_k (v2_k - v1_k); x1 = x + v2 dt, x2 = SHAKE(x1 | bonds of x),
+ * Wp = (1/dt^2) sum_clusters lambda_c sum_k loc_k (x) m_k (x2_k - x1_k).  loc_k: minimum-image vector from the cluster's first atom to atom k at the
+ * unmoved coordinates; lambda_c: the smallest per-atom lambda of the cluster (1 when mhip_set_atoms got none).  Wv + Wp is ADDED to 9 host doubles
+ * (row-major, [3a + b] = loc_a * impulse_b).
+ * f_xyz: the total forces, caller order, packed xyz, the context's precision, host or device (mem_kind), virtual-site rows already distributed
+ * (mhip_distribute_forces).  dt [ps]: the preview step, 0.0005 in the reference; the result depends on it at first order.  parts18 (nullable): Wv then
+ * Wp, WRITTEN.  n_not_converged (nullable): cluster-solves of THIS call that stopped at max_iters (mhip_constraint_info's count is the step loops').
+ * The trial runs in double precision per cluster with the dist_tol and max_iters of mhip_set_constraints.  Read-only: coordinates, velocities, lists
+ * and the forces kept for a continued run stay as they were, and two calls give the same bits.  Without constraints: success, nothing added.
+ * MHIP_ERR_INVALID for a null f_xyz or virial9 or a dt that is not positive and finite; MHIP_ERR_STATE before mhip_set_atoms / mhip_set_state. */
+int32_t mhip_constraint_virial(mhip_ctx* ctx, const void* f_xyz, int32_t mem_kind, double dt,
+                               double* virial9, double* parts18, int64_t* n_not_converged);
 
 /* ---- virtual sites (src/virtual.jl) ------------------------------------------------------------------------------------------------ */
 /* n sites; type 1/2/3/4 = OneParticleSite / TwoParticleAverageSite / ThreeParticleAverageSite / OutOfPlaneSite (virtual.jl:10-22);

@@ -109,3 +109,17 @@ struct MhipLaunchTrial
     j_split::Int32
     us_per_pass::Float32
 end
+
+# ---- raw wrappers (no reference generic is overridden) ----------------------------------------------------------------
+# mhip_constraint_virial: the constraint contribution to the virial at the coordinates and velocities the context holds, by the trial step of
+# merge_initial_constraint_virial! (simulators.jl:459-495; per-cluster accumulation shake.jl:234-392), ADDED to virial9 (3×3, row-major); parts18 is
+# written with the RATTLE part then the SHAKE part.  f: the total forces in the context's precision (3 × n_atoms, the memory order of
+# Array(reinterpret(T, fs))), virtual-site rows already distributed.  Returns the cluster solves of this call that stopped at max_iters.  For a pressure
+# logger or a Julia-side barostat of a constrained System, next to the force virial of mhip_forces / mhip_specific_virial / mhip_general_virial.
+function constraint_virial!(virial9::Vector{Float64}, parts18::Vector{Float64}, c::HipContext, f::Array{T}; dt::Float64=0.0005) where {T<:Union{Float32, Float64}}
+    (length(virial9) == 9 && length(parts18) == 18) || error("libmollyhip: constraint_virial! takes 9 and 18 doubles")
+    n_not_converged = Ref{Int64}(0)
+    check(c, ccall((:mhip_constraint_virial, libmollyhip), Int32, (Ptr{Cvoid}, Ptr{T}, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Ref{Int64}),
+                   c.ptr, f, 0, dt, virial9, parts18, n_not_converged))
+    return n_not_converged[]
+end

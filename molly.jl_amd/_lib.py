@@ -159,6 +159,7 @@ SIGNATURES = {
     "mhip_domain_info": (_I32, [_P, C.POINTER(_I64 * 8)]),
     "mhip_set_constraints": (_I32, [_P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _D, _D, _I32]),
     "mhip_constraint_info": (_I32, [_P, C.POINTER(_I64 * 8)]),
+    "mhip_constraint_virial": (_I32, [_P, _P, _I32, _D, _P, _P, C.POINTER(_I64)]),
     "mhip_set_virtual_sites": (_I32, [_P, _I64, _P, _P, _P, _P, _P, _P]),
     "mhip_place_virtual_sites": (_I32, [_P]),
     "mhip_distribute_forces": (_I32, [_P, _P, _I32]),

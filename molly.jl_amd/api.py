@@ -707,10 +707,43 @@ def place_virtual_sites(sys):
     return sys
 
 
-def virial(sys, step_n=0, pairwise=True, specific=True, general=True):
+_forces_of = forces      # (constraint_virial takes an argument of that name)
+
+
+def constraint_virial(sys, forces=None, dt=0.0005, parts=False):
+    """The constraint contribution to the virial at the current coordinates and velocities, 3×3, by the reference's trial step
+    (merge_initial_constraint_virial!, simulators.jl:459-495; per-cluster accumulation shake.jl:234-392): RATTLE, a kick by dt and RATTLE, a drift by dt
+    and SHAKE, all on the device in double precision (mhip_constraint_virial); the System is left as it was.  forces: the total forces, (n, 3), virtual-site
+    rows distributed (None: forces(sys)).  dt [ps]: the preview step, the reference's 0.0005 by default — the result depends on it at first order.
+    parts=True: (W, Wv, Wp), the RATTLE and the SHAKE part.  Zeros without constraints."""
+    if not (isinstance(dt, (int, float, np.floating)) and math.isfinite(dt) and dt > 0):
+        raise ValueError("dt must be positive and finite")
+    n = len(sys)
+    if forces is not None:
+        forces = np.ascontiguousarray(forces, dtype=sys.dtype)
+        if forces.shape != (n, 3):
+            raise ValueError(f"forces must have the shape ({n}, 3), not {forces.shape}")
+    w = np.zeros(9, np.float64); p18 = np.zeros(18, np.float64)
+    if sys.constraints:
+        if forces is None:
+            forces = _forces_of(sys)
+        sys.push_state(velocities=True)
+        bad = C.c_int64(0)
+        sys._check(_lib.lib().mhip_constraint_virial(sys._ctx, sys._ptr(forces), _lib.MEM_HOST, float(dt), w.ctypes.data_as(C.c_void_p),
+                                                     p18.ctypes.data_as(C.c_void_p), C.byref(bad)))
+        if bad.value:
+            warnings.warn(f"constraint_virial: {bad.value} cluster solves stopped at max_iters")
+    w = w.reshape(3, 3)
+    return (w, p18[:9].reshape(3, 3), p18[9:].reshape(3, 3)) if parts else w
+
+
+def virial(sys, step_n=0, pairwise=True, specific=True, general=True, constraints=False):
     """virial(sys): 3×3 tensor Σ r ⊗ f of the pairwise (over the neighbour pairs, force.jl:848-852), specific (force.jl:991-1060) and
-    general (PME reciprocal space, ewald.jl:701-723, 925-927) interactions (energy.jl:116-131)."""
-    sys._refuse_constrained("virial")
+    general (PME reciprocal space, ewald.jl:701-723, 925-927) interactions (energy.jl:116-131).
+    constraints=True adds constraint_virial(sys) (the reference's virial(sys) always does, compute_initial_total_virial!, simulators.jl:529-536); a
+    constrained System is refused without it, as it has been.  Making the term the default is a later, separate change of behaviour."""
+    if not constraints:
+        sys._refuse_constrained("virial")
     if any(vs.type == 4 for vs in sys.virtual_sites):
         raise MollyHipError(-6, "OutOfPlaneSite is not currently compatible with virial calculation (virtual.jl:112)")
     L = _lib.lib()
@@ -724,24 +757,27 @@ def virial(sys, step_n=0, pairwise=True, specific=True, general=True):
         sys._check(L.mhip_specific_virial(sys._ctx, vp))
     if general and sys.general_inters:
         sys._check(L.mhip_general_virial(sys._ctx, vp))
-    return v.reshape(3, 3)
+    v = v.reshape(3, 3)
+    if constraints and sys.constraints:
+        v = v + constraint_virial(sys, forces(sys, step_n))
+    return v
 
 
-def scalar_virial(sys, step_n=0):
+def scalar_virial(sys, step_n=0, constraints=False):
     """scalar_virial(sys) = tr(virial(sys)) (energy.jl:148-151)"""
-    return float(np.trace(virial(sys, step_n)))
+    return float(np.trace(virial(sys, step_n, constraints=constraints)))
 
 
-def pressure(sys, step_n=0):
-    """pressure(sys) = (2K + W) / V with K = ½ Σ m v ⊗ v (spatial.jl:930-982), in kJ mol⁻¹ nm⁻³ (1 kJ mol⁻¹ nm⁻³ = 16.6054 bar)"""
-    w = virial(sys, step_n)
+def pressure(sys, step_n=0, constraints=False):
+    """pressure(sys) = (2K + W) / V with K = ½ Σ m v ⊗ v (spatial.jl:930-982), in kJ mol⁻¹ nm⁻³ (1 kJ mol⁻¹ nm⁻³ = 16.6054 bar); constraints: as virial's"""
+    w = virial(sys, step_n, constraints=constraints)
     v = np.asarray(sys.velocities, dtype=np.float64); m = np.asarray(sys.masses, dtype=np.float64)
     k = 0.5 * np.einsum("i,ia,ib->ab", m, v, v)
     return (2.0 * k + w) / float(np.prod(sys.boundary.side_lengths))
 
 
-def scalar_pressure(sys, step_n=0):
-    return float(np.trace(pressure(sys, step_n))) / 3.0
+def scalar_pressure(sys, step_n=0, constraints=False):
+    return float(np.trace(pressure(sys, step_n, constraints=constraints))) / 3.0
 
 
 def potential_energy(sys, step_n=0, pairwise=True, specific=True, general=True):

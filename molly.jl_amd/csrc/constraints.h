@@ -81,4 +81,17 @@ void launch_con_step(hipStream_t s, int n_blocks, int mode, const ConP<T>& C, co
 // X (nullable): a step on which a rescaling thermostat applies (thermostat_step.h), launched as k_con_thermo with one more kernel argument — mode 2 is its close launch
 // and leaves the thermostat partials in X->th_out, mode 0 its open launch and reads them (X->th_in) beside A.cm_in.  The uncoupled launches' arguments are what they were.
 
+// The constraint contribution to the virial at the state held (mhip_constraint_virial): the reference's trial step — RATTLE, kick by dt + RATTLE, drift by dt +
+// SHAKE (merge_initial_constraint_virial!, simulators.jl:459-495) — per cluster in double, read-only.  f: the total forces, caller order, packed xyz; lam
+// (nullable: 1): the per-atom λ, caller order; part: 19 component-major runs of n_blocks partials (Wv[9], Wp[9], the solves that stopped at max_iters).
+template <class T> struct ConVirial {
+    using T4 = typename Vec<T>::T4;
+    const T4* pos; const T4* vel; const T* f; const T* lam;
+    double dt;
+    double* part;
+};
+// n_blocks <= 1024 workgroups of CON_BLOCK lanes over the items [0, C.end[CK_ANGLE]); C.stat and the hosted sites are not read
+template <class T>
+void launch_con_virial(hipStream_t s, int n_blocks, const ConP<T>& C, const ConVirial<T>& A, const GridP<T>& G);
+
 }  // namespace mhip

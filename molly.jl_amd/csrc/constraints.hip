@@ -579,4 +579,183 @@ void launch_con_step(hipStream_t s, int nb, int mode, const ConP<T>& C, const Co
 template void launch_con_step<float>(hipStream_t, int, int, const ConP<float>&, const ConStep<float>&, const GridP<float>&, const ThermoArgs*);
 template void launch_con_step<double>(hipStream_t, int, int, const ConP<double>&, const ConStep<double>&, const GridP<double>&, const ThermoArgs*);
 
+// ---- the constraint virial of the state held (mhip_constraint_virial; merge_initial_constraint_virial!, simulators.jl:459-495) ------------
+namespace {
+
+// The trial step is carried in double, relative to the cluster's first atom: x[k] is the minimum-image vector first atom → atom k of the UNMOVED
+// coordinates (shake.jl:239-243's local_coord), and the virial is accumulated from the solvers' own corrections dv[] and D[] — never from a
+// difference of values rounded to T (a SHAKE correction of the preview step is some 1e-5 nm, an fp32 ulp at 3 nm 2.4e-7 nm).
+
+// RATTLE as rattle() above, on bond vectors r and velocities v in double: dv[k] is the correction of atom k, v is left as it was
+template <int K> __device__ inline void vir_rattle(const double (*r)[3], const double (*v)[3], const double* im, double (*dv)[3]) {
+    constexpr int NA = Shape<K>::NA, NC = Shape<K>::NC;
+    double A[3][3] = {}, b[3] = {};
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const double u[3] = {v[cb<K>(c)][0] - v[ca<K>(c)][0], v[cb<K>(c)][1] - v[ca<K>(c)][1], v[cb<K>(c)][2] - v[ca<K>(c)][2]};
+        b[c] = -dot3(r[c], u);
+#pragma unroll
+        for (int e = 0; e < NC; ++e) A[c][e] = kcoef<K>(c, e, im) * dot3(r[c], r[e]);
+    }
+    solve<NC>(A, b);
+#pragma unroll
+    for (int k = 0; k < NA; ++k) {
+        dv[k][0] = dv[k][1] = dv[k][2] = 0;
+#pragma unroll
+        for (int e = 0; e < NC; ++e) {
+            const double w = (double)((k == cb<K>(e)) - (k == ca<K>(e))) * b[e] * im[k];
+            dv[k][0] += w * r[e][0]; dv[k][1] += w * r[e][1]; dv[k][2] += w * r[e][2];
+        }
+    }
+}
+
+// SHAKE as shake() above, on drifted positions q relative to the first atom: D[k] is the correction of atom k along the bonds r0 of the unmoved
+// coordinates.  Returns the iterations taken, negative when max_iters ran out first.
+template <int K> __device__ inline int vir_shake(const double (*r0)[3], const double (*q)[3], const double* im, const double* dl, double tol, int max_iters, double (*D)[3]) {
+    constexpr int NA = Shape<K>::NA, NC = Shape<K>::NC;
+    double g[NC] = {};
+#pragma unroll
+    for (int k = 0; k < NA; ++k) D[k][0] = D[k][1] = D[k][2] = 0;
+    int it = 0; bool done = false;
+    for (;;) {
+        double s[NC][3], sig[3] = {};
+        done = true;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int a = ca<K>(c), b = cb<K>(c);
+#pragma unroll
+            for (int x = 0; x < 3; ++x) s[c][x] = (q[b][x] + D[b][x]) - (q[a][x] + D[a][x]);
+            const double s2 = dot3(s[c], s[c]);
+            sig[c] = s2 - dl[c] * dl[c];
+            done = done && fabs(sqrt(s2) - dl[c]) <= tol;
+        }
+        if (done || it >= max_iters) break;
+        ++it;
+        if constexpr (NC == 1) {
+            const double kc = kcoef<K>(0, 0, im), a = kc * kc * dot3(r0[0], r0[0]), b = 2.0 * kc * dot3(s[0], r0[0]), c = sig[0];
+            const double disc = b * b - 4.0 * a * c;
+            g[0] += (disc >= 0 && b > 0) ? -2.0 * c / (b + sqrt(disc)) : -c / b;      // the root nearer zero; Newton if there is none
+        } else {
+            double J[3][3] = {}, rhs[3] = {};
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                rhs[c] = -sig[c];
+#pragma unroll
+                for (int e = 0; e < NC; ++e) J[c][e] = 2.0 * kcoef<K>(c, e, im) * dot3(s[c], r0[e]);
+            }
+            solve<NC>(J, rhs);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) g[c] += rhs[c];
+        }
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            D[k][0] = D[k][1] = D[k][2] = 0;
+#pragma unroll
+            for (int e = 0; e < NC; ++e) {
+                const double w = (double)((k == cb<K>(e)) - (k == ca<K>(e))) * g[e] * im[k];
+                D[k][0] += w * r0[e][0]; D[k][1] += w * r0[e][1]; D[k][2] += w * r0[e][2];
+            }
+        }
+    }
+    return done ? it : -it;
+}
+
+// W[0..8] += λ_c/dt · Σ_k x_k ⊗ m_k dv_k (RATTLE of the kicked velocities), W[9..17] += λ_c/dt² · Σ_k x_k ⊗ m_k D_k (SHAKE of the drifted positions);
+// row-major, W[3a + b] = x_a · impulse_b (shake.jl:244-246)
+template <class T, int K>
+__device__ inline void con_virial_item(const ConP<T>& C, const ConVirial<T>& A, const GridP<T>& G, int64_t t, double* W, int& n_fail) {
+    constexpr int NA = Shape<K>::NA, NC = Shape<K>::NC;
+    if (C.atoms[4 * t] < 0) return;      // padding of a kind's last wave
+    double x[NA][3], v[NA][3], kick[NA][3], m[NA], im[NA], lam = 1.0;
+#pragma unroll
+    for (int k = 0; k < NA; ++k) {
+        const int32_t id = C.atoms[4 * t + k], sl = C.inv[id];
+        const auto p = A.pos[sl], u = A.vel[sl];
+        m[k] = (double)u.w; im[k] = u.w == T(0) ? 0.0 : 1.0 / (double)u.w;
+        x[k][0] = p.x; x[k][1] = p.y; x[k][2] = p.z;
+        v[k][0] = u.x; v[k][1] = u.y; v[k][2] = u.z;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) kick[k][c] = u.w == T(0) ? 0.0 : (double)A.f[3 * (int64_t)id + c] / m[k] * A.dt;      // accels .* dt (:482)
+        if (A.lam) lam = fmin(lam, (double)A.lam[id]);                                                                    // MinimumMixing (constraints.jl:94-117)
+    }
+#pragma unroll
+    for (int k = NA - 1; k >= 0; --k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            double d = x[k][c] - x[0][c];
+            if (G.periodic[c]) d -= (double)G.L[c] * rint(d / (double)G.L[c]);
+            x[k][c] = d;
+        }
+    double r[NC][3], dv[NA][3];
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) r[c][a] = x[cb<K>(c)][a] - x[ca<K>(c)][a];
+    vir_rattle<K>(r, v, im, dv);                                                                                          // :479, accumulates nothing
+#pragma unroll
+    for (int k = 0; k < NA; ++k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[k][c] += dv[k][c] + kick[k][c];                                                     // :482
+    vir_rattle<K>(r, v, im, dv);                                                                                          // :484
+    const double sv = lam / A.dt, sp = lam / (A.dt * A.dt);
+#pragma unroll
+    for (int k = 1; k < NA; ++k)
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) W[3 * a + b] += sv * x[k][a] * (m[k] * dv[k][b]);
+    double q[NA][3], D[NA][3];
+#pragma unroll
+    for (int k = 0; k < NA; ++k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[k][c] += dv[k][c];
+#pragma unroll
+    for (int k = 0; k < NA; ++k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) q[k][c] = x[k][c] + (v[k][c] - v[0][c]) * A.dt;                                       // :486, relative to the first atom
+    const double dl[3] = {C.d[4 * t], C.d[4 * t + 1], C.d[4 * t + 2]};
+    const int it = vir_shake<K>(r, q, im, dl, C.tol, C.max_iters, D);                                                     // :488
+    n_fail += it < 0;
+#pragma unroll
+    for (int k = 1; k < NA; ++k)
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) W[9 + 3 * a + b] += sp * x[k][a] * (m[k] * D[k][b]);
+}
+
+// one lane per cluster of the kinds CK_2 … CK_ANGLE (a wave stays within one kind), a grid-stride loop, one wave per block; reads pos, vel, λ and the
+// caller's forces, writes nothing but part[c · gridDim.x + block], c < 18 the components of Wv then Wp, c = 18 the solves that stopped at max_iters
+template <class T>
+__global__ void __launch_bounds__(CON_BLOCK) k_con_virial(ConP<T> C, ConVirial<T> A, GridP<T> G) {
+    double W[18] = {};
+    int nf = 0;
+    const int64_t n = C.end[CK_ANGLE], stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += stride) {
+        if (t < C.end[CK_2]) con_virial_item<T, CK_2>(C, A, G, t, W, nf);
+        else if (t < C.end[CK_3]) con_virial_item<T, CK_3>(C, A, G, t, W, nf);
+        else if (t < C.end[CK_4]) con_virial_item<T, CK_4>(C, A, G, t, W, nf);
+        else con_virial_item<T, CK_ANGLE>(C, A, G, t, W, nf);
+    }
+#pragma unroll
+    for (int c = 0; c < 18; ++c) {
+        double w = W[c];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) w += __shfl_xor(w, o, 64);
+        if (threadIdx.x == 0) A.part[(size_t)c * gridDim.x + blockIdx.x] = w;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) nf += __shfl_xor(nf, o, 64);
+    if (threadIdx.x == 0) A.part[(size_t)18 * gridDim.x + blockIdx.x] = (double)nf;
+}
+
+}  // namespace
+
+template <class T>
+void launch_con_virial(hipStream_t s, int nb, const ConP<T>& C, const ConVirial<T>& A, const GridP<T>& G) {
+    hipLaunchKernelGGL(k_con_virial<T>, dim3(nb), dim3(CON_BLOCK), 0, s, C, A, G);
+}
+template void launch_con_virial<float>(hipStream_t, int, const ConP<float>&, const ConVirial<float>&, const GridP<float>&);
+template void launch_con_virial<double>(hipStream_t, int, const ConP<double>&, const ConVirial<double>&, const GridP<double>&);
+
 }  // namespace mhip

@@ -105,6 +105,7 @@ struct EngineBase {
     virtual void domain_info(int64_t*) = 0;
     virtual void set_constraints(int64_t, const int32_t*, const int32_t*, const double*, int64_t, const int32_t*, const int32_t*, const int32_t*, const double*, double, double, int32_t) = 0;
     virtual void constraint_info(int64_t*) = 0;
+    virtual void constraint_virial(const void*, int, double, double*, double*, int64_t*) = 0;
     virtual bool constrained() const = 0;
     virtual void set_virtual_sites(int64_t, const int32_t*, const int32_t*, const int32_t*, const int32_t*, const int32_t*, const double*) = 0;
     virtual void place_virtual_sites() = 0;
@@ -1390,6 +1391,8 @@ template <class T> class Engine final : public EngineBase {
         const T* de = to_device(ep, n_tot, mem_kind, s3);
         const T* dm = to_device(ms, n_tot, mem_kind, s4);
         const T* dl = to_device(lam, n_tot, mem_kind, s5);
+        atom_lam_set = dl != nullptr;      // kept in caller order for the constraint virial (constraint_virial_lambda, constraints.jl:94-117)
+        if (dl) { atom_lam.reserve(n_tot); MHIP_HIP(hipMemcpyAsync(atom_lam.p, dl, n_tot * sizeof(T), hipMemcpyDeviceToDevice, stream)); }
         hipLaunchKernelGGL(k_scatter_params<T>, dim3(cdiv(n_tot, 256)), dim3(256), 0, stream, n_tot, (const int32_t*)inv.p, dq, ds, de, dm, dl, pos[cur].p, vel[cur].p, lj[cur].p);
         MHIP_HIP(hipGetLastError());
         MHIP_HIP(hipStreamSynchronize(stream));
@@ -2719,6 +2722,42 @@ template <class T> class Engine final : public EngineBase {
         out8[0] = con.n_kind[0]; out8[1] = con.n_kind[1]; out8[2] = con.n_kind[2]; out8[3] = con.n_kind[3];
         out8[4] = con_on ? con.n_constraints : 0; out8[5] = con_last_max; out8[6] = con_fails; out8[7] = 0;
     }
+    // The constraint contribution to the virial at the coordinates and velocities held, by the reference's trial step (merge_initial_constraint_virial!,
+    // simulators.jl:459-495; per-cluster accumulation shake.jl:234-392), ADDED to virial9; parts18 (nullable) = Wv then Wp, written.  Read-only: k_con_virial
+    // writes partials into red_part and nothing else, so coordinates, velocities, lists, kept forces and the held.h records stand as they were.
+    DBuf<T> atom_lam; bool atom_lam_set = false;
+    void constraint_virial(const void* f_xyz, int mem_kind, double dt, double* virial9, double* parts18, int64_t* n_not_converged) override {
+        if (!f_xyz || !virial9) throw ApiError{MHIP_ERR_INVALID, "constraint_virial: null force or virial buffer"};
+        if (!(dt > 0) || !std::isfinite(dt)) throw ApiError{MHIP_ERR_INVALID, "constraint_virial: dt must be positive and finite"};
+        if (parts18) std::fill(parts18, parts18 + 18, 0.0);
+        if (n_not_converged) *n_not_converged = 0;
+        if (!con_on) return;                                                      // length(sys.constraints) > 0 (:472)
+        if (!held.state_set() || !held.params_set()) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before constraint_virial"};
+        flush_cm();
+        const T* df = (const T*)f_xyz;
+        if (mem_kind == MHIP_MEM_HOST) {
+            const size_t count = 3 * (size_t)cfg.n_atoms;
+            stage_a.reserve(count); df = stage_a.p;
+            MHIP_HIP(hipMemcpyAsync(stage_a.p, f_xyz, count * sizeof(T), hipMemcpyHostToDevice, stream));
+        }
+        const int nb = std::max(1, std::min(cdiv(con.end[CK_ANGLE], CON_BLOCK), 1024));
+        red_part.reserve(19 * (size_t)nb);
+        ConP<T> C{};
+        C.atoms = con_atoms.p; C.d = con_d.p; C.inv = inv.p; for (int k = 0; k < CK_N; ++k) C.end[k] = con.end[k];
+        C.tol = con_tol; C.max_iters = con_iters;                                 // (no C.stat: the step loops' counters are theirs)
+        ConVirial<T> A{};
+        A.pos = pos[cur].p; A.vel = vel[cur].p; A.f = df; A.lam = atom_lam_set ? (const T*)atom_lam.p : nullptr; A.dt = dt; A.part = red_part.p;
+        tr("k_con_virial");
+        prof.begin(7, stream);
+        launch_con_virial<T>(stream, nb, C, A, G);
+        prof.end(7, stream);
+        MHIP_HIP(hipGetLastError());
+        double w[19];
+        for (int c = 0; c < 19; ++c) w[c] = sum_run((const double*)red_part.p + (size_t)c * nb, nb);
+        for (int c = 0; c < 9; ++c) virial9[c] += w[c] + w[9 + c];
+        if (parts18) std::copy(w, w + 18, parts18);
+        if (n_not_converged) *n_not_converged = (int64_t)std::llround(w[18]);
+    }
     int con_blocks() const { return std::max(1, std::min(cdiv(con.n_items(), CON_BLOCK), 1024)); }      // (<= 1024: the Σ m v partials fit a half of cm_step)
     void con_run_start() { MHIP_HIP(hipMemsetAsync(con_stat.p + 1, 0, sizeof(unsigned long long), stream)); }
     // the solver's counters travel with the run's closing synchronisation: no read-back inside the step loop
@@ -3129,6 +3168,9 @@ int32_t mhip_set_constraints(mhip_ctx* ctx, int64_t n_dist, const int32_t* i, co
     NEED_CTX(); return guard(ctx, [&] { ctx->e->set_constraints(n_dist, i, j, dist, n_angle, ai, aj, ak, d3, dist_tol, vel_tol, max_iters); });
 }
 int32_t mhip_constraint_info(mhip_ctx* ctx, int64_t* out8) { NEED_CTX(); return guard(ctx, [&] { if (!out8) throw mhip::ApiError{MHIP_ERR_INVALID, "null output"}; ctx->e->constraint_info(out8); }); }
+int32_t mhip_constraint_virial(mhip_ctx* ctx, const void* f, int32_t mk, double dt, double* virial9, double* parts18, int64_t* n_not_converged) {
+    NEED_CTX(); return guard(ctx, [&] { ctx->e->constraint_virial(f, mk, dt, virial9, parts18, n_not_converged); });
+}
 int32_t mhip_set_virtual_sites(mhip_ctx* ctx, int64_t n, const int32_t* type, const int32_t* site, const int32_t* a1, const int32_t* a2, const int32_t* a3, const double* w6) {
     NEED_CTX(); return guard(ctx, [&] { ctx->e->set_virtual_sites(n, type, site, a1, a2, a3, w6); });
 }
