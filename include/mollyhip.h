@@ -307,9 +307,10 @@ int32_t mhip_set_andersen(mhip_ctx* ctx, double kT, double prob, uint64_t seed);
  * R is k = 0, S the sum of the squares of 1 <= k <= dof − 1.  dof <= 0 or K <= 0 leaves the velocities alone (λ = 1), as does a negative λ² of
  * kinds 1 and 2 (the reference's sqrt domain error).  Constraints, virtual sites, bonded terms, PME, a TriclinicBoundary and both precisions are
  * supported: a uniform scale commutes with RATTLE.  MHIP_ERR_INVALID for a kind outside 0..3, kT, coupling_const or n_steps not positive, n_steps != 1
- * for kinds 1 and 2; MHIP_ERR_UNSUPPORTED next to the Andersen coupling, with ghosts or a domain plan (in either call order); the split step, the halo
- * entry points (mhip_set_halo_plan, mhip_vv_halo_start / _mid / _begin / _end / _end_parts, each with a check of its own), mhip_set_domain,
- * mhip_domain_run and mhip_langevin_run refuse a context with a thermostat set.  Kind 0 restores a context that never had one. */
+ * for kinds 1 and 2; MHIP_ERR_UNSUPPORTED next to the Andersen coupling, with ghosts, a halo plan, a domain plan or peers (in either call order);
+ * the split step, the halo entry points (mhip_set_halo_plan, mhip_vv_halo_start / _mid / _begin / _end / _end_parts), mhip_halo_region with
+ * world > 1, mhip_set_domain, mhip_domain_run and mhip_langevin_run refuse a context with a thermostat set (one table decides every such
+ * refusal: csrc/admit.h).  Kind 0 restores a context that never had one. */
 int32_t mhip_set_thermostat(mhip_ctx* ctx, int32_t kind, double kT, double coupling_const, int32_t n_steps, int64_t dof,
                             uint64_t philox_key, uint64_t philox_ctr1);
 /* out[8]: applications since set; step of the last one; its λ; its K before scaling [kJ/mol]; smallest and largest λ since set;
@@ -322,9 +323,10 @@ int32_t mhip_philox4x32_10(const uint32_t* ctr4, const uint32_t* key2, uint32_t*
 /* dist_constraints (i, j, dist) and angle_constraints given as their three distances (i, j = centre, k, d_ij, d_jk, d_ik; constraints.jl:38-53).
  * 0-based caller indices, host arrays, double lengths.  n_dist = n_angle = 0 removes the constraints.  Clusters are built as build_clusters does
  * (constraints.jl:251-344): a central atom with 1, 2 or 3 distance constraints, or an angle triangle; MHIP_ERR_INVALID for an atom in two clusters,
- * more than three constraints on one centre, a chain, a ring, a linear angle or an index out of range.  MHIP_ERR_UNSUPPORTED with ghosts or a domain
- * plan, a TriclinicBoundary, or the Andersen coupling (mhip_set_andersen, prob > 0); the split step (mhip_vv_init / stage1 / stage2) and the halo
- * paths refuse a constrained context.  mhip_vv_run and mhip_langevin_run then apply RATTLE after every kick and SHAKE (with the velocity correction
+ * more than three constraints on one centre, a chain, a ring, a linear angle or an index out of range.  MHIP_ERR_UNSUPPORTED with ghosts, a halo
+ * plan, a domain plan or peers, a TriclinicBoundary, or the Andersen coupling (mhip_set_andersen, prob > 0), in either call order; the split step
+ * (mhip_vv_init / stage1 / stage2), every halo entry point (mhip_vv_halo_end / _end_parts and mhip_set_halo_plan included), mhip_halo_region with
+ * world > 1, mhip_set_domain and mhip_domain_run refuse a constrained context.  mhip_vv_run and mhip_langevin_run then apply RATTLE after every kick and SHAKE (with the velocity correction
  * v += Δx/dt) after every drift, in the reference's order (simulators.jl:589-620, 1155-1185).  The virials (virial9 of mhip_forces, mhip_*_virial)
  * stay the force virials: they leave out the constraint contribution (shake.jl:205-470), which mhip_constraint_virial computes on request for the
  * state held.  The solves run in double precision; RATTLE is one exact linear solve per cluster, so vel_tol is only checked to be positive. */
@@ -355,8 +357,9 @@ int32_t mhip_constraint_virial(mhip_ctx* ctx, const void* f_xyz, int32_t mem_kin
  * weight_cross [1/nm]); host arrays.  n = 0 removes the sites: the context then steps as one that never had any.
  * Validation as setup_virtual_sites (virtual.jl:120-180): MHIP_ERR_INVALID for a type outside 1..4, an index out of range, an atom defined as a
  * site twice, a parent that is itself a site, a site that is in a constraint (either call order with mhip_set_constraints), weights of a type 2 / 3
- * site that do not sum to 1 (isapprox).  MHIP_ERR_UNSUPPORTED with ghosts or a domain plan, a TriclinicBoundary or the Andersen coupling; the split
- * step and the halo paths refuse a context with sites.  mhip_vv_run and mhip_langevin_run then serve every site inside the work item that owns all
+ * site that do not sum to 1 (isapprox).  MHIP_ERR_UNSUPPORTED with ghosts, a halo plan, a domain plan or peers, a TriclinicBoundary or the Andersen
+ * coupling, in either call order; the split step, every halo entry point (mhip_vv_halo_end / _end_parts and mhip_set_halo_plan included),
+ * mhip_halo_region with world > 1, mhip_set_domain and mhip_domain_run refuse a context with sites.  mhip_vv_run and mhip_langevin_run then serve every site inside the work item that owns all
  * of its parents (a constraint cluster, a free atom, or 2..4 free atoms joined for the purpose): its force joins the parents' before every kick, its
  * position follows them after every drift, its velocity is left alone.  They refuse (when the run starts) a site with a non-zero mass
  * (MHIP_ERR_INVALID) and a site no single item can host (MHIP_ERR_UNSUPPORTED: parents in two constraint clusters, or a union of free parents above

@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "list_policy.h"
 #include "held.h"
+#include "admit.h"
 #include "replan.h"
 #include "halo_step.h"
 #include "forces_launch.h"
@@ -106,12 +107,10 @@ struct EngineBase {
     virtual void set_constraints(int64_t, const int32_t*, const int32_t*, const double*, int64_t, const int32_t*, const int32_t*, const int32_t*, const double*, double, double, int32_t) = 0;
     virtual void constraint_info(int64_t*) = 0;
     virtual void constraint_virial(const void*, int, double, double*, double*, int64_t*) = 0;
-    virtual bool constrained() const = 0;
     virtual void set_virtual_sites(int64_t, const int32_t*, const int32_t*, const int32_t*, const int32_t*, const int32_t*, const double*) = 0;
     virtual void place_virtual_sites() = 0;
     virtual void distribute_forces(void*, int) = 0;
     virtual void virtual_site_info(int64_t*) = 0;
-    virtual bool has_sites() const = 0;
     virtual void domain_export(int64_t*, void*) = 0;
 };
 
@@ -256,6 +255,23 @@ template <class T> class Engine final : public EngineBase {
     DBuf<T4> frc_side; const T4* pend_a = nullptr;
 
     Held held;      // what the context holds and what voids it: changed only through its events (held.h)
+    // the context as admit.h's table sees it, and the one question every entry point asks first.  granted: modes the call at hand does not need (see the table's notes)
+    uint32_t modes() const {
+        bool peers_open = xf.region.p != nullptr;
+        for (int r = 0; peers_open && r < xf.world; ++r) peers_open = xf.peers.region[r] != nullptr;
+        const bool f[adm::N_MODES] = {held.state_set(), held.params_set(), n_ghost > 0, dom.ready, xf.world > 1, tri_mode != 0, con_on, vs_on, thermo_on(), andersen_prob > 0,
+                                      hp_set, xf.routes || (hp_set && hp.n_cm_peers == 0 && hp.n_send_rows == 0), xf.region.p != nullptr, peers_open, held.frc_valid(),
+                                      pme.on(), has_exc, caller_indexed_topology()};
+        uint32_t m = 0;
+        for (int k = 0; k < adm::N_MODES; ++k) m |= (f[k] ? 1u : 0u) << k;
+        return m;
+    }
+    void admit(adm::Entry e, uint32_t granted = 0) const {
+        static_assert((int)adm::Code::N_CODES == 3, "admit.h answers OK, UNSUPPORTED or STATE: one code of mollyhip.h each");
+        static const int32_t code_of[] = {MHIP_OK, MHIP_ERR_UNSUPPORTED, MHIP_ERR_STATE};
+        const adm::Verdict v = adm::admit(e, modes() | granted);
+        if (v.code != adm::Code::OK) throw ApiError{code_of[(int)v.code], std::string(adm::row(e).name) + " " + v.why};
+    }
     bool minimg = false; int64_t n_set_state_refresh = 0;
     int64_t last_build_step = std::numeric_limits<int64_t>::min();
     int64_t n_rebuilds = 0, n_force_calls = 0, n_gs_passes = 0; double last_rebuild_ms = 0;
@@ -461,8 +477,7 @@ template <class T> class Engine final : public EngineBase {
     // two HIP events.  Shapes whose tile does not fit the LDS, or that the build had to shrink, are reported with us_per_pass < 0 /
     // under the shape they ended in.  A shape set by mhip_set_launch_config is replaced by the winner.
     int tune_launch(int n_passes, mhip_launch_trial* trials, int max_trials) override {
-        if (!held.state_set() || !held.params_set()) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before tuning"};
-        if (n_ghost > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "launch shapes are tuned on single-domain contexts (the ranks of a decomposition must agree on one)"};
+        admit(adm::TUNE);      // (the ranks of a decomposition must agree on one shape: single domain)
         if (n_passes < 1) throw ApiError{MHIP_ERR_INVALID, "n_passes must be positive"};
         static const int cand[][2] = {{256, 4}, {256, 2}, {128, 8}, {128, 4}, {128, 2}, {64, 16}, {64, 8}};
         flush_cm();
@@ -560,9 +575,9 @@ template <class T> class Engine final : public EngineBase {
     }
 
     void rebuild_impl(int64_t step_n) {
+        admit(adm::SEARCH);
         lp.next_check_step = -1;
         const int sub_bits = (ilog2(2 * G.ncell + 1) + 1 + 6 <= 32) ? 6 : 0;      // atoms of a cell ordered by a 6-bit Morton position inside it
-        if (!held.params_set() || !held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before forces"};
         auto t0 = std::chrono::steady_clock::now();
         const int o = cur, n = 1 - cur;
         const int ncell2 = 2 * G.ncell + 1;
@@ -582,8 +597,8 @@ template <class T> class Engine final : public EngineBase {
                            (const T4*)frc[o].p, (const T2*)lj[o].p, (const int32_t*)orig[o].p, pos[n].p, vel[n].p, frc[n].p, lj[n].p, orig[n].p, inv.p);
         prof.end(3, stream);
         cur = n;
-        if (n_ghost > 0 && has_exc) throw ApiError{MHIP_ERR_UNSUPPORTED, "exclusion lists with ghost atoms are not supported"};
-        if (tri_mode && !tri_grid && n_tot + 8 > TILE_SLOT_MAX) throw ApiError{MHIP_ERR_UNSUPPORTED, "a TriclinicBoundary whose cell heights allow no cell grid (fewer than 6 cells of r_list/2 on every axis) is limited to 32 759 atoms"};
+        if (tri_mode && !tri_grid && n_tot + 8 > TILE_SLOT_MAX)      // (depends on the atoms and the box handed over: not a row of admit.h)
+            throw ApiError{MHIP_ERR_UNSUPPORTED, "a TriclinicBoundary whose cell heights allow no cell grid (fewer than 6 cells of r_list/2 on every axis) is limited to 32 759 atoms"};
 
         for (int attempt = 0; attempt < 12; ++attempt) {
             n_blocks = cdiv(n_owned, BI);
@@ -1281,7 +1296,7 @@ template <class T> class Engine final : public EngineBase {
     // (second kick, or fold_side_forces).  req: see PassReq, whose fuse_* this decides.
     PassRes step_forces(int64_t step_n, PassReq req = PassReq{}) {
         pass_step = step_n;
-        if (pme.on() && n_ghost > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "PME runs on a single domain (SURVEY §8(e): 6mrr-size systems are replicas only)"};
+        if (n_ghost > 0) admit(adm::FORCE_PASS);      // (the row refuses next to ghosts only — PME runs on a single domain, SURVEY §8(e) — so a single domain does not ask per step)
         // (group-split passes leave partial forces that the per-atom sums of the bonded slots fold in: only where such a launch follows)
         const bool gs_ok = bonded.any() && n_ghost == 0;
         const bool small_fused = bonded.any() && pme.on() && n_ghost == 0;
@@ -1340,7 +1355,7 @@ template <class T> class Engine final : public EngineBase {
 
     void launch_pme_forces() {
         if (!pme.on()) return;
-        if (n_ghost > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "PME runs on a single domain (SURVEY §8(e): 6mrr-size systems are replicas only)"};
+        if (n_ghost > 0) admit(adm::FORCE_PASS);
         prof.begin(6, stream);
         pme.run(stream, n_owned, pos[cur].p, frc[cur].p, nullptr);
         prof.end(6, stream);
@@ -1360,11 +1375,8 @@ template <class T> class Engine final : public EngineBase {
     }
 
     void set_atom_counts(int64_t no, int64_t ng) override {
+        if (ng > 0) admit(adm::ON_GHOSTS);
         if (no <= 0 || ng < 0 || no + ng > cap) throw ApiError{MHIP_ERR_INVALID, "atom counts exceed the context capacity"};
-        if (ng > 0 && tri_mode) throw ApiError{MHIP_ERR_UNSUPPORTED, "TriclinicBoundary is single-domain"};
-        if (ng > 0 && con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain"};
-        if (ng > 0 && vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites run on a single domain"};
-        if (ng > 0 && thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain"};
         n_owned = no; n_ghost = ng; n_tot = no + ng;
         pending_cm.none(); hp_set = false; halo_cm_in = false;
         new_local_atoms(false);
@@ -1522,7 +1534,7 @@ template <class T> class Engine final : public EngineBase {
     }
 
     void specific_forces(int accumulate, void* f_xyz, int mem_kind) override {
-        if (!held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_state must be called before specific_forces"};
+        admit(adm::SPECIFIC_FORCES);
         MHIP_HIP(hipMemsetAsync(frc[cur].p, 0, (size_t)n_tot * sizeof(T4), stream));
         bonded.launch_forces(stream, G, I, pos[cur].p, inv.p, frc[cur].p, orig[cur].p, n_owned, cap);
         held.forces_partial();
@@ -1565,17 +1577,16 @@ template <class T> class Engine final : public EngineBase {
     }
     // Σ over the specific interactions of r ⊗ f (force.jl:991-1060), ADDED to out9
     void specific_virial(double* out9) override {
-        if (!held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_state must be called before specific_virial"};
+        admit(adm::SPECIFIC_VIRIAL);
         const int nb = bonded.launch_virial(stream, G, I, pos[cur].p, inv.p, red_part);
         if (!nb) return;
         for (int c = 0; c < 9; ++c) out9[c] += sum_run((const double*)red_part.p + (size_t)c * nb, nb);
     }
     // reciprocal-space PME virial (recip_conv_inner! ewald.jl:701-723, halved :747-750) + the net-charge term charge_E·I (:925-927), ADDED to out9
     void general_virial(double* out9) override {
-        if (!held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_state must be called before general_virial"};
+        admit(adm::GENERAL_VIRIAL);
         if (!pme.on()) return;
-        const double e = general_potential_energy();           // fills red_part with the 7 component-major runs (and Σq)
-        (void)e;
+        (void)pme_energy();                                     // fills red_part with the 7 component-major runs (and Σq)
         const int nb = pme.conv_blocks();
         double v[6];
         for (int c = 0; c < 6; ++c) v[c] = 0.5 * sum_run((const double*)red_part.p + (size_t)(c + 1) * nb, nb);
@@ -1585,7 +1596,7 @@ template <class T> class Engine final : public EngineBase {
     }
 
     double specific_potential_energy() override {
-        if (!held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_state must be called before specific_potential_energy"};
+        admit(adm::SPECIFIC_ENERGY);
         int n_part = bonded.launch_energy(stream, G, I, pos[cur].p, inv.p, red_part);
         if (n_part == 0) return 0.0;
         return read_sum(n_part);
@@ -1594,13 +1605,11 @@ template <class T> class Engine final : public EngineBase {
     // TriclinicBoundary(v1, v2, v3; approx_images) (spatial.jl:131-220).  cfg.box must hold (v1.x, v2.y, v3.z).  Single domain,
     // systems that fit one tile (every block sees every atom; all distances by the exact in-loop minimum image).
     void set_triclinic(const double* bv9, int32_t approx_images) override {
+        admit(adm::ON_TRICLINIC);
         if (!(bv9[0] > 0) || bv9[1] != 0 || bv9[2] != 0) throw ApiError{MHIP_ERR_INVALID, "first basis vector must be along the x-axis (no y or z component) and have a positive x component"};
         if (!(bv9[4] > 0) || bv9[5] != 0) throw ApiError{MHIP_ERR_INVALID, "second basis vector must be in the xy plane (no z component) and have a positive y component"};
         if (!(bv9[8] > 0)) throw ApiError{MHIP_ERR_INVALID, "third basis vector must have a positive z component"};
         for (int d = 0; d < 3; ++d) if (!cfg.periodic[d]) throw ApiError{MHIP_ERR_UNSUPPORTED, "TriclinicBoundary is periodic on all three axes"};
-        if (n_ghost > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "TriclinicBoundary: single domain"};
-        if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints with a TriclinicBoundary are not supported"};
-        if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites with a TriclinicBoundary are not supported"};
         if (std::fabs(bv9[0] - cfg.box[0]) > 1e-12 * bv9[0] || std::fabs(bv9[4] - cfg.box[1]) > 1e-12 * bv9[4] || std::fabs(bv9[8] - cfg.box[2]) > 1e-12 * bv9[8])
             throw ApiError{MHIP_ERR_INVALID, "the context's box must be (v1.x, v2.y, v3.z) of the triclinic basis"};
         MHIP_HIP(hipStreamSynchronize(stream));
@@ -1616,7 +1625,7 @@ template <class T> class Engine final : public EngineBase {
     // PME mesh and α, the launch shape and the velocities are kept; the cell grid, the capacities and the reciprocal box are made again, every list is
     // dropped, and the coordinates must be handed over again (they were scaled with the box): mhip_set_state.
     void set_box(const double* box3, const double* bv9) override {
-        if (n_ghost > 0 || dom.ready || xf.world > 1) throw ApiError{MHIP_ERR_UNSUPPORTED, "set_box: single domain (the bricks of a decomposition are cut from the box: plan again)"};
+        admit(adm::SET_BOX);      // (the bricks of a decomposition are cut from the box: plan again)
         for (int d = 0; d < 3; ++d) if (!(box3[d] > 0) || std::isinf(box3[d]) || std::isnan(box3[d])) throw ApiError{MHIP_ERR_INVALID, "box side lengths must be positive and finite"};
         if ((tri_mode != 0) != (bv9 != nullptr)) throw ApiError{MHIP_ERR_INVALID, tri_mode ? "set_box: the context has a TriclinicBoundary, its basis vectors are needed" : "set_box: basis vectors given for a context without a TriclinicBoundary"};
         if (bv9) {
@@ -1654,16 +1663,18 @@ template <class T> class Engine final : public EngineBase {
     }
     // ≙ AtomsCalculators.forces! of the general interaction (force.jl:792-795): forces added to / written into f_xyz
     void general_forces(int accumulate, void* f_xyz, int mem_kind) override {
-        if (!held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_state must be called before general_forces"};
+        admit(adm::GENERAL_FORCES);
         MHIP_HIP(hipMemsetAsync(frc[cur].p, 0, (size_t)n_tot * sizeof(T4), stream));
         launch_pme_forces();
         held.forces_partial();
         export_frc(accumulate, f_xyz, mem_kind);
     }
     double general_potential_energy() override {
-        if (!held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_state must be called before general_potential_energy"};
-        if (!pme.on()) return 0.0;
-        if (n_ghost > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "PME runs on a single domain"};
+        admit(adm::GENERAL_ENERGY);
+        return pme.on() ? pme_energy() : 0.0;
+    }
+    double pme_energy() {
+        admit(adm::FORCE_PASS);
         if (!pc_valid) {   // Σq and Σq² (ewald.jl:917-924) from the charges kept in pos.w
             std::vector<T4> hp(n_owned);
             MHIP_HIP(hipStreamSynchronize(stream));
@@ -1744,8 +1755,8 @@ template <class T> class Engine final : public EngineBase {
     // (simulators.jl:564-571), which yields the same numbers from the same lists in the same order.
     const bool reuse_run_forces = env_int("MOLLYHIP_REUSE_RUN_FORCES", 1) != 0;
     int64_t n_reused_starts = 0;
-    void vv_init(int64_t first_step) override {
-        if (!held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_state must be called before vv_run"};
+    void vv_init(int64_t first_step) override { admit(adm::VV_INIT); init_impl(first_step); }
+    void init_impl(int64_t first_step) {
         lists_after_set_state();           // (a set_state that brought the SAME coordinates leaves the forces valid)
         const bool had = held.reusable_run_forces() && reuse_run_forces;
         const int64_t reb0 = n_outer, fil0 = n_filters; const bool inner0 = held.inner_valid();   // (searches re-sort, prunes change the list walked)
@@ -1755,11 +1766,8 @@ template <class T> class Engine final : public EngineBase {
         step_forces(first_step);
         fold_side_forces();
     }
-    void vv_stage1(double dt) override {
-        if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no constraints: use mhip_vv_run"};
-        if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no virtual sites: use mhip_vv_run"};
-        if (thermo_on() && !in_run) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no rescaling thermostat: use mhip_vv_run"};
-        if (!held.frc_valid()) throw ApiError{MHIP_ERR_STATE, "vv_stage1 needs forces from vv_init / vv_stage2"};
+    void vv_stage1(double dt) override { admit(adm::VV_STAGE1); stage1_impl(dt); }
+    void stage1_impl(double dt) {      // first kick + drift: the forces of the coordinates held are in place
         lp.cur_dt = dt;
         tr("k_vv1");
         prof.begin(2, stream);
@@ -1793,9 +1801,7 @@ template <class T> class Engine final : public EngineBase {
         if (due && !dual) refresh(step_n);
     }
     void vv_stage2(int64_t step_n, double dt) override {
-        if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no constraints: use mhip_vv_run"};
-        if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no virtual sites: use mhip_vv_run"};
-        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no rescaling thermostat: use mhip_vv_run"};
+        admit(adm::VV_STAGE2);
         stage2_cadenced(step_n, dt, false);
         MHIP_HIP(hipGetLastError());
     }
@@ -1803,7 +1809,7 @@ template <class T> class Engine final : public EngineBase {
     // the same with this rank's Σ m v left as n_parts per-block partials {Px, Py, Pz, M} in cm_parts_dev (no finalize launch): the
     // host all-reduces the whole array and hands it back through remove_cm_parts_dev, where the next first kick re-sums it
     void halo_end_parts(int64_t step_n, double dt, int64_t first, int64_t n, const void* in_dev, double* cm_parts_dev, int32_t n_parts) override {
-        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain, stepped by mhip_vv_run"};
+        admit(adm::HALO_END_PARTS);
         if (cm_parts_dev && (n_parts < 1 || n_parts > 1024)) throw ApiError{MHIP_ERR_INVALID, "n_parts must be 1..1024"};
         scatter_coords(first, n, in_dev);
         stage2_cadenced(step_n, dt, cm_parts_dev != nullptr, cm_parts_dev, n_parts);
@@ -1887,7 +1893,7 @@ template <class T> class Engine final : public EngineBase {
     DBuf<double> cm_all;         // [0] this rank's {ΣPx, ΣPy, ΣPz, ΣM} of the step before (k_halo_pack), [1 + p] peer p's (k_halo_unpack)
     void set_halo_plan(const mhip_halo_plan* p) override {
         if (!p) { hp_set = false; return; }
-        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain, stepped by mhip_vv_run"};
+        admit(adm::ON_HALO_PLAN);
         if (p->n_recv_rows < 0 || p->n_send_rows < 0 || p->n_cm_peers < 0 || p->n_cm_peers > 26 || p->cm_rows < 0 || p->cm_rows > 4 || p->n_send_cm < 0)
             throw ApiError{MHIP_ERR_INVALID, "halo plan: counts out of range"};
         if ((p->n_recv_rows > 0 && (!p->recv || !p->recv_dst)) || (p->n_send_rows > 0 && (!p->send || !p->send_idx || !p->send_shift)) || (p->n_send_cm > 0 && !p->send_cm_pos))
@@ -1914,19 +1920,17 @@ template <class T> class Engine final : public EngineBase {
     }
     // first kick + drift + pack: after vv_init, after a step that stopped behind its second kick, after a re-plan
     void halo_start(double dt) override {
-        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain, stepped by mhip_vv_run"};
-        if (!hp_set) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_plan first"};
-        vv_stage1(dt);
-        halo_pack(false);
-        halo_cm_in = false;
+        admit(adm::HALO_START);
+        halo_start_impl(dt);
     }
+    void halo_start_impl(double dt) { stage1_impl(dt); halo_pack(false); halo_cm_in = false; }
     // flags bit 0: this step removes the centre-of-mass motion; bit 1: stop behind the second kick (the step's Σ m v goes to
     // cm_parts_dev as n_parts per-block partials for an all-reduce, nothing is packed) — at the rebuild cadence and at the end of a run
     void halo_mid(int64_t step_n, double dt, int32_t flags, double* cm_parts_dev, int32_t n_parts) override {
-        if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain, stepped by mhip_vv_run / mhip_langevin_run"};
-        if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites run on a single domain, stepped by mhip_vv_run / mhip_langevin_run"};
-        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain, stepped by mhip_vv_run"};
-        if (!hp_set) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_plan first"};
+        admit(adm::HALO_MID);
+        halo_mid_impl(step_n, dt, flags, cm_parts_dev, n_parts);
+    }
+    void halo_mid_impl(int64_t step_n, double dt, int32_t flags, double* cm_parts_dev, int32_t n_parts) {
         const bool cm = (flags & 1) != 0, last = (flags & 2) != 0;
         if (cm && last && (!cm_parts_dev || n_parts < 1 || n_parts > 1024)) throw ApiError{MHIP_ERR_INVALID, "n_parts must be 1..1024"};
         if (cm && !last && hp.cm_rows <= 0 && hp.n_cm_peers > 0) throw ApiError{MHIP_ERR_INVALID, "halo plan carries no centre-of-mass rows"};
@@ -1993,6 +1997,7 @@ template <class T> class Engine final : public EngineBase {
     // this rank's receive region: two halves of rows_cap rows of 3 reals behind the header, fine-grained device memory (peers write it,
     // this device polls it); its IPC handle goes to every peer
     void halo_region(int64_t rows_cap, int32_t world, int32_t my_rank, void* handle_out) override {
+        if (world > 1) admit(adm::ON_PEERS);
         if (rows_cap <= 0 || world < 1 || world > XFER_MAX_RANKS || my_rank < 0 || my_rank >= world) throw ApiError{MHIP_ERR_INVALID, "halo region: rows / world / rank out of range"};
         MHIP_HIP(hipStreamSynchronize(stream));
         if (!xf.region.p || xf.rows_cap < rows_cap || xf.world != world || xf.rank != my_rank) {
@@ -2024,7 +2029,7 @@ template <class T> class Engine final : public EngineBase {
         }
     }
     void halo_open_peer(int32_t rank, const void* handle) override {
-        if (!xf.region.p) throw ApiError{MHIP_ERR_STATE, "mhip_halo_region first"};
+        admit(adm::OPEN_PEER);
         if (rank < 0 || rank >= xf.world || !handle) throw ApiError{MHIP_ERR_INVALID, "halo peer: rank out of range or null handle"};
         if (rank == xf.rank) return;
         hipIpcMemHandle_t h; std::memcpy(&h, handle, sizeof(h));
@@ -2041,9 +2046,8 @@ template <class T> class Engine final : public EngineBase {
     // where the rows of the current ghost plan travel: consecutive segments of the send buffer → (peer, first row in the peer's half)
     void set_halo_routes(const mhip_halo_routes* rt) override {
         if (!rt) { xf.routes = false; return; }
-        if (!hp_set) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_plan first"};
+        admit(adm::SET_ROUTES, rt->n_peers > 0 ? 0 : adm::REGION);      // (routes without peers need no region)
         if (rt->n_peers < 0 || rt->n_peers >= XFER_MAX_RANKS) throw ApiError{MHIP_ERR_INVALID, "halo routes: peer count out of range"};
-        if (rt->n_peers > 0 && !xf.region.p) throw ApiError{MHIP_ERR_STATE, "mhip_halo_region first"};
         std::vector<int32_t> rp, rd; rp.reserve((size_t)hp.n_send_rows); rd.reserve((size_t)hp.n_send_rows);
         int64_t recv_total = 0;
         xf.peer_rank.assign(rt->peer_rank, rt->peer_rank + rt->n_peers);
@@ -2066,8 +2070,7 @@ template <class T> class Engine final : public EngineBase {
     // into every rank's table and waits (bounded) for all of theirs.  0 = some rank's store did not become visible here within 2 s —
     // the host then keeps its own loop with torch.distributed collectives (every rank must call this at the same point).
     int halo_selftest() override {
-        if (!xf.region.p) throw ApiError{MHIP_ERR_STATE, "mhip_halo_region first"};
-        for (int r = 0; r < xf.world; ++r) if (!xf.peers.region[r]) throw ApiError{MHIP_ERR_STATE, "mhip_halo_open_peer for every rank first"};
+        admit(adm::SELFTEST);
         const float token[4] = {(float)(xf.rank + 1), 0.f, 0.f, 0.f};
         MHIP_HIP(hipMemcpyAsync(xf.mine3.p, token, 3 * sizeof(float), hipMemcpyHostToDevice, stream));
         ++xf.plan_seq;
@@ -2123,12 +2126,8 @@ template <class T> class Engine final : public EngineBase {
     // step taken removes the centre-of-mass motion, cm_parts_dev holds its n_parts partials for the all-reduce over the ranks
     // (mhip_remove_cm_parts_dev), as after mhip_vv_halo_mid with the stop flag.  counters[0..2] += checks, prunes arranged, re-plans asked.
     void domain_run(int64_t first_step, int64_t n_steps, double dt, int32_t remove_cm_every, double* cm_parts_dev, int32_t n_parts, int64_t* steps_done, int32_t* reason, int64_t* counters) override {
-        if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain, stepped by mhip_vv_run / mhip_langevin_run"};
-        if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites run on a single domain, stepped by mhip_vv_run / mhip_langevin_run"};
-        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain, stepped by mhip_vv_run"};
-        if (!hp_set) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_plan first"};
+        admit(adm::DOMAIN_RUN, n_steps > 0 ? 0 : adm::FORCES);      // (a run of no steps kicks nothing)
         const bool solo = hp.n_cm_peers == 0 && hp.n_send_rows == 0;
-        if (!solo && !xf.routes) throw ApiError{MHIP_ERR_STATE, "mhip_set_halo_routes first"};
         xf_plan_words(); xf.world = std::max(xf.world, 1);      // (a run without a region: one brick)
         *steps_done = 0; *reason = 0;
         if (n_steps <= 0) return;
@@ -2158,7 +2157,7 @@ template <class T> class Engine final : public EngineBase {
             return;
         }
         struct Direct { bool& f; explicit Direct(bool& b) : f(b) { f = true; } ~Direct() { f = false; } } guard_direct(xf_direct);   // packs send, unpacks wait
-        halo_start(dt);
+        halo_start_impl(dt);
         // a check carried over from the previous call belongs to that call's last step; a caller that continues somewhere else gets a
         // fresh one at its first step instead
         if (xf.plan_pending && xf.plan_step != first_step) { xf.plan_pending = false; xf.next_check = first_step + 1; }
@@ -2170,7 +2169,8 @@ template <class T> class Engine final : public EngineBase {
                 xf.plan_pending = false;
                 // an exchange timed out somewhere before this check: the steps since ran on stale ghost rows and the triple may be partial
                 // (ranks could decide differently) — give the chunk up here instead of queueing the rest of it
-                if (xf.world > 1 && xf.h_red3[3] != 0.f) { xf_check_errors(); throw ApiError{MHIP_ERR_STATE, "ghost exchange timed out"}; }
+                const bool timed_out = xf.world > 1 && xf.h_red3[3] != 0.f;
+                if (timed_out) { xf_check_errors(); throw ApiError{MHIP_ERR_STATE, "ghost exchange timed out"}; }
                 int32_t check_in = 0;
                 const float red[3] = {xf.h_red3[0], xf.h_red3[1], xf.h_red3[2]};
                 // A check issued at a step whose own force pass went on to prune (or search) measured lists that no longer exist — a check asked for k steps
@@ -2202,7 +2202,7 @@ template <class T> class Engine final : public EngineBase {
             }
             if (debug_on) std::fprintf(stderr, "[mhip %d] %.3f step %lld separate launches (reads exchange %u) replan %d stop %d inner_valid %d\n", xf.rank, now_ms(), (long long)s, xf.seq, (int)replan_here, (int)stop, (int)held.inner_valid());
             if (n_ghost > 0 && xf.n_peers > 0 && !replan_here) (void)halo_interior(s);          // the blocks that need no ghost, while the peers' rows arrive
-            halo_mid(s, dt, (cm ? 1 : 0) | (stop ? 2 : 0), (cm && stop) ? cm_parts_dev : nullptr, (cm && stop) ? n_parts : 0);   // waits + unpacks … packs + sends
+            halo_mid_impl(s, dt, (cm ? 1 : 0) | (stop ? 2 : 0), (cm && stop) ? cm_parts_dev : nullptr, (cm && stop) ? n_parts : 0);   // waits + unpacks … packs + sends
             ++*steps_done;
             // (a check issued at the LAST step of this call stays pending: the first step of the next call reads it, one step late like any
             // other — dropping it here left the inner list unvouched for until the next multiple of `every`, up to 2·every steps after the
@@ -2235,10 +2235,7 @@ template <class T> class Engine final : public EngineBase {
     // each, the face thresholds in T — every number formed the way the host planner forms it, so that both planners select the same atoms
     void set_domain(const mhip_domain_geometry* gm, const int64_t* gids_dev) override {
         if (!gm) { dom.ready = false; return; }
-        if (con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain"};
-        if (vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites run on a single domain"};
-        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain"};
-        if (caller_indexed_topology()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the in-engine re-plan moves atoms between ranks and resets the caller order: contexts with bonded terms, exception lists, special pairs or PME keep the host planner"};
+        admit(adm::ON_DOMAIN_PLAN);
         const int gx = gm->grid[0], gy = gm->grid[1], gz = gm->grid[2];
         if (gx < 1 || gy < 1 || gz < 1 || (int64_t)gx * gy * gz > XFER_MAX_RANKS) throw ApiError{MHIP_ERR_INVALID, "domain geometry: 1 .. 64 bricks"};
         const int world = gx * gy * gz, me = gm->rank;
@@ -2297,7 +2294,7 @@ template <class T> class Engine final : public EngineBase {
         out8[0] = n_owned; out8[1] = n_ghost; out8[2] = dom.n_replans; out8[3] = dom.n_migrated; out8[4] = (int64_t)std::llround(dom.plan_ms * 1e3); out8[5] = (int64_t)std::llround(dom.search_ms * 1e3); out8[6] = out8[7] = 0;
     }
     void domain_export(int64_t* gid_dev, void* par4_dev) override {
-        if (!dom.ready) throw ApiError{MHIP_ERR_STATE, "mhip_set_domain first"};
+        admit(adm::DOMAIN_EXPORT);
         hipLaunchKernelGGL(k_rp_export<T>, dim3(cdiv(n_owned, 256)), dim3(256), 0, stream, n_owned, (const int32_t*)inv.p, (const T4*)pos[cur].p, (const T4*)vel[cur].p, (const T2*)lj[cur].p,
                            (const int64_t*)dom.gid[dom.gcur].p, gid_dev, (T*)par4_dev);
         MHIP_HIP(hipGetLastError());
@@ -2408,8 +2405,8 @@ template <class T> class Engine final : public EngineBase {
 
     // one MD step of a ghosted sub-domain in two calls around the ghost exchange
     void halo_begin(double dt, const int32_t* idx_dev, const void* shift_dev, int64_t n, void* out_dev) override {
-        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain, stepped by mhip_vv_run"};
-        vv_stage1(dt);
+        admit(adm::HALO_BEGIN);
+        stage1_impl(dt);
         gather_coords(idx_dev, shift_dev, n, out_dev);
     }
     // Between halo_begin and halo_end, while the ghost coordinates travel: the pair forces of the blocks whose tile holds no ghost.
@@ -2423,7 +2420,7 @@ template <class T> class Engine final : public EngineBase {
         return 1;
     }
     void halo_end(int64_t step_n, double dt, int64_t first, int64_t n, const void* in_dev, double* cm_out4_dev) override {
-        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain, stepped by mhip_vv_run"};
+        admit(adm::HALO_END);
         scatter_coords(first, n, in_dev);
         stage2_cadenced(step_n, dt, cm_out4_dev != nullptr);
         if (cm_out4_dev) {   // this rank's {ΣPx, ΣPy, ΣPz, ΣM} for the all-reduce; nothing pending locally: the TOTAL comes back via remove_cm_dev
@@ -2456,13 +2453,12 @@ template <class T> class Engine final : public EngineBase {
     }
 
     void vv_run(int64_t first_step, int64_t n_steps, double dt, int remove_cm_every) override {
-        if (!held.state_set() || !held.params_set()) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before vv_run"};
-        if (n_ghost > 0) throw ApiError{MHIP_ERR_STATE, "vv_run is single-domain; drive ghosted domains with vv_stage1/vv_stage2"};
+        admit(adm::VV_RUN);      // (ghosted domains are driven by the halo entry points or mhip_domain_run)
         lp.cur_dt = dt;
         InRun guard_in_run(in_run);
         sites_run_start();                                                        // :561-562
         if (first_step == 0 && remove_cm_every != 0) remove_cm();                 // simulators.jl:563
-        vv_init(first_step);                                                      // :564-571
+        init_impl(first_step);                                                    // :564-571
         if (items_on()) con_run_start();
         vv_loop(first_step, n_steps, dt, remove_cm_every, nullptr, 0);
         flush_cm();
@@ -2494,10 +2490,10 @@ template <class T> class Engine final : public EngineBase {
                 con_launch(0, con_blocks(), dt, nullptr, false, nullptr);
                 prof.end(2, stream);
                 drifted();
-            } else vv_stage1(dt);
+            } else stage1_impl(dt);
         }
         for (int64_t step = first_step + 1; step <= last; ++step) {
-            if (!fused) vv_stage1(dt);                                            // :594-609
+            if (!fused) stage1_impl(dt);                                          // :594-609
             // find_neighbors at step % n_steps == 0 (:645, neighbors.jl:396) builds the list from the coordinates of THIS step; it is
             // scheduled before the force pass so that, with the dual pair list, that pass can prune the outer list on the way.
             // Forces are unaffected: the pass walks a superset of the old list and every interaction has a cutoff <= r_list.
@@ -2549,12 +2545,11 @@ template <class T> class Engine final : public EngineBase {
     ThermoP thermo; DBuf<double> thermo_part, thermo_info_dev; Pinned<double> h_thermo; double thermo_host[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     bool thermo_on() const { return thermo.kind != THERMO_OFF; }
     void set_thermostat(int32_t kind, double kT, double tau, int32_t n_steps, int64_t dof, uint64_t key, uint64_t ctr1) override {
+        if (kind != THERMO_OFF) admit(adm::ON_THERMOSTAT);
         if (kind < THERMO_OFF || kind > THERMO_CSVR) throw ApiError{MHIP_ERR_INVALID, "thermostat kind must be 0 (off), 1 (Immediate), 2 (Berendsen) or 3 (VelocityRescale)"};
         if (kind != THERMO_OFF) {
             if (!(kT > 0) || !(tau > 0) || n_steps < 1) throw ApiError{MHIP_ERR_INVALID, "thermostat: kT, coupling_const and n_steps must be positive"};
             if (kind != THERMO_CSVR && n_steps != 1) throw ApiError{MHIP_ERR_INVALID, "thermostat: ImmediateThermostat and BerendsenThermostat apply every step (n_steps = 1)"};
-            if (andersen_prob > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "a rescaling thermostat next to the Andersen coupling is not supported"};
-            if (n_ghost > 0 || dom.ready || hp_set || xf.world > 1) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats run on a single domain"};
         }
         thermo = ThermoP{};
         if (kind == THERMO_OFF) return;      // the context steps as one that never had a thermostat (the record of the last one stays readable)
@@ -2598,7 +2593,6 @@ template <class T> class Engine final : public EngineBase {
     ClusterSet con; DBuf<int32_t> con_atoms; DBuf<double> con_d; DBuf<unsigned long long> con_stat; Pinned<unsigned long long> h_con;
     bool con_on = false; double con_tol = 1e-8; int32_t con_iters = 25;
     int64_t con_last_max = 0, con_fails = 0;
-    bool constrained() const override { return con_on; }
     void set_constraints(int64_t n_dist, const int32_t* ci, const int32_t* cj, const double* dist, int64_t n_angle, const int32_t* ai, const int32_t* aj,
                          const int32_t* ak, const double* d3, double dist_tol, double vel_tol, int32_t max_iters) override {
         if (n_dist == 0 && n_angle == 0) {      // removal: the context steps as one that never had constraints
@@ -2606,9 +2600,7 @@ template <class T> class Engine final : public EngineBase {
             build_items(con_in, sites);
             return;
         }
-        if (n_ghost > 0 || dom.ready || xf.world > 1) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints run on a single domain"};
-        if (tri_mode) throw ApiError{MHIP_ERR_UNSUPPORTED, "constraints with a TriclinicBoundary are not supported"};
-        if (andersen_prob > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen thermostat with constraints is not supported (a re-drawn velocity breaks RATTLE)"};
+        admit(adm::ON_CONSTRAINTS);      // (Andersen: a re-drawn velocity breaks RATTLE)
         if (!(dist_tol > 0) || !(vel_tol > 0) || max_iters < 1) throw ApiError{MHIP_ERR_INVALID, "constraints: tolerances must be positive and max_iters at least 1"};
         if (n_dist < 0 || n_angle < 0 || (n_dist > 0 && (!ci || !cj || !dist)) || (n_angle > 0 && (!ai || !aj || !ak || !d3))) throw ApiError{MHIP_ERR_INVALID, "constraints: negative count or null array"};
         ConIn in;
@@ -2646,16 +2638,13 @@ template <class T> class Engine final : public EngineBase {
     // ---- virtual sites (virtual_sites.h): the one-shot entry points; inside the step loops the sites are hosted by the items above -----------
     SiteSet sites; bool vs_on = false, vs_place_due = false, vs_mass_ok = false;
     DBuf<int32_t> vs_item, vs_hrec, vs_rec; DBuf<double> vs_hw, vs_w; DBuf<uint8_t> vs_flag;
-    bool has_sites() const override { return vs_on; }
     void set_virtual_sites(int64_t n, const int32_t* type, const int32_t* site, const int32_t* a1, const int32_t* a2, const int32_t* a3, const double* w6) override {
         if (n == 0) {      // removal: the context steps as one that never had sites
             vs_on = false; vs_place_due = false; sites = SiteSet{}; vs_rec.release(); vs_w.release(); vs_flag.release();
             build_items(con_in, sites);
             return;
         }
-        if (n_ghost > 0 || dom.ready || xf.world > 1) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites run on a single domain"};
-        if (tri_mode) throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual sites with a TriclinicBoundary are not supported"};
-        if (andersen_prob > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen thermostat with virtual sites is not supported"};
+        admit(adm::ON_SITES);
         SiteSet vs = build_sites(cfg.n_atoms, n, type, site, a1, a2, a3, w6);
         build_items(con_in, vs);                // (a site in a constraint: MHIP_ERR_INVALID here, as in mhip_set_constraints when that comes second)
         std::vector<int32_t> rec(8 * (size_t)n, 0);
@@ -2669,8 +2658,8 @@ template <class T> class Engine final : public EngineBase {
     VsP<T> vs_params() const { VsP<T> V{}; V.n = sites.n; V.rec = vs_rec.p; V.w = vs_w.p; V.inv = inv.p; return V; }
     // place_virtual_sites! on the coordinates the context holds.  To the lists and the forces this is a set_state of the sites' rows: the same protocol
     // (a site that already sat where its parents put it changes nothing, so a run continued in chunks finds its forces and lists as it left them)
-    void place_virtual_sites() override {
-        if (!held.state_set()) throw ApiError{MHIP_ERR_STATE, "set_state must be called before place_virtual_sites"};
+    void place_virtual_sites() override { admit(adm::PLACE_SITES); place_sites(); }
+    void place_sites() {
         vs_place_due = false;
         if (!vs_on) return;
         state_write_begins();
@@ -2682,7 +2671,7 @@ template <class T> class Engine final : public EngineBase {
     // distribute_forces! in place on the caller's packed xyz array (caller order); r12, r13 of an OutOfPlaneSite from the context's coordinates
     void distribute_forces(void* f_xyz, int mem_kind) override {
         if (!vs_on) return;
-        if (!held.state_set() && sites.n_type[3] > 0) throw ApiError{MHIP_ERR_STATE, "set_state must be called before distribute_forces (OutOfPlaneSite)"};
+        admit(adm::DISTRIBUTE_FORCES, sites.n_type[3] > 0 ? 0 : adm::STATE);      // (r12, r13 of an OutOfPlaneSite come from the coordinates held)
         T* d = (T*)f_xyz;
         const size_t count = 3 * (size_t)cfg.n_atoms;
         if (mem_kind == MHIP_MEM_HOST) { stage_a.reserve(count); d = stage_a.p; MHIP_HIP(hipMemcpyAsync(d, f_xyz, count * sizeof(T), hipMemcpyHostToDevice, stream)); }
@@ -2700,8 +2689,6 @@ template <class T> class Engine final : public EngineBase {
     // placed if coordinates came in since they last were (simulators.jl:561-562, 1113-1114)
     void sites_run_start() {
         if (!vs_on) return;
-        if (!held.state_set() || !held.params_set()) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before a run"};
-        if (andersen_prob > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen thermostat with virtual sites is not supported"};
         if (con.first_unhosted >= 0)
             throw ApiError{MHIP_ERR_UNSUPPORTED, "virtual site " + std::to_string(con.first_unhosted) + " (atom " + std::to_string(sites.site[con.first_unhosted]) +
                            ") cannot be hosted by one work item: its parents lie in two constraint clusters, or in a union of free parents above four atoms"};
@@ -2715,7 +2702,7 @@ template <class T> class Engine final : public EngineBase {
                     throw ApiError{MHIP_ERR_INVALID, "virtual site " + std::to_string(k) + " (atom " + std::to_string(sites.site[k]) + ") has a non-zero mass: the step loops need massless sites"};
             vs_mass_ok = true;
         }
-        if (vs_place_due) place_virtual_sites();
+        if (vs_place_due) place_sites();
     }
     // clusters of 2 / 3 / 4 atoms, angle clusters, constraints, the most SHAKE iterations of the last run, solves stopped at max_iters since set, spare
     void constraint_info(int64_t* out8) override {
@@ -2727,12 +2714,12 @@ template <class T> class Engine final : public EngineBase {
     // writes partials into red_part and nothing else, so coordinates, velocities, lists, kept forces and the held.h records stand as they were.
     DBuf<T> atom_lam; bool atom_lam_set = false;
     void constraint_virial(const void* f_xyz, int mem_kind, double dt, double* virial9, double* parts18, int64_t* n_not_converged) override {
+        admit(adm::CONSTRAINT_VIRIAL, con_on ? 0 : adm::STATE | adm::PARAMS);      // (without constraints the call reads nothing)
         if (!f_xyz || !virial9) throw ApiError{MHIP_ERR_INVALID, "constraint_virial: null force or virial buffer"};
         if (!(dt > 0) || !std::isfinite(dt)) throw ApiError{MHIP_ERR_INVALID, "constraint_virial: dt must be positive and finite"};
         if (parts18) std::fill(parts18, parts18 + 18, 0.0);
         if (n_not_converged) *n_not_converged = 0;
         if (!con_on) return;                                                      // length(sys.constraints) > 0 (:472)
-        if (!held.state_set() || !held.params_set()) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before constraint_virial"};
         flush_cm();
         const T* df = (const T*)f_xyz;
         if (mem_kind == MHIP_MEM_HOST) {
@@ -2790,9 +2777,8 @@ template <class T> class Engine final : public EngineBase {
     }
     // mode 0: one application of the Andersen thermostat with per-atom probability `prob` (coupling.jl:196-211);
     // mode 1: random_velocities! (spatial.jl:803-831).  Velocities only: positions, forces and the pair list stay valid.
-    void redraw_velocities(int mode, double kT, double prob, uint64_t key, uint64_t ctr1) override {
-        if (!held.state_set() || !held.params_set()) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before drawing velocities"};
-        if (n_ghost > 0) throw ApiError{MHIP_ERR_UNSUPPORTED, "velocity draws are single-domain"};
+    void redraw_velocities(int mode, double kT, double prob, uint64_t key, uint64_t ctr1) override { admit(adm::REDRAW); redraw_impl(mode, kT, prob, key, ctr1); }
+    void redraw_impl(int mode, double kT, double prob, uint64_t key, uint64_t ctr1) {
         if (!(kT >= 0)) throw ApiError{MHIP_ERR_INVALID, "kT must be non-negative"};
         StochP<T> P = stoch_params(kT, key, ctr1);
         const double pc = std::min(std::max(prob, 0.0), std::nextafter(1.0, 0.0));          // clamp(…, 0, prevfloat(1.0))
@@ -2805,24 +2791,20 @@ template <class T> class Engine final : public EngineBase {
     // the reference draws (ctr1, key) from the host rng per step — here they are the words of philox(step, 0; seed)
     double andersen_kT = 0, andersen_prob = 0; uint64_t andersen_seed = 0;
     void set_andersen(double kT, double prob, uint64_t seed) override {
-        if (prob > 0 && con_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen thermostat with constraints is not supported (a re-drawn velocity breaks RATTLE)"};
-        if (prob > 0 && vs_on) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen thermostat with virtual sites is not supported"};
-        if (prob > 0 && thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the Andersen coupling next to a rescaling thermostat is not supported"};
+        if (prob > 0) admit(adm::ON_ANDERSEN);
         andersen_kT = kT; andersen_prob = prob; andersen_seed = seed;
     }
     void apply_coupling(int64_t step) {
         if (!(andersen_prob > 0)) return;
         uint32_t w[4]; philox_host((uint64_t)step, 0, andersen_seed, w);
-        redraw_velocities(0, andersen_kT, andersen_prob, ((uint64_t)w[3] << 32) | w[2], ((uint64_t)w[1] << 32) | w[0]);
+        redraw_impl(0, andersen_kT, andersen_prob, ((uint64_t)w[3] << 32) | w[2], ((uint64_t)w[1] << 32) | w[0]);
     }
 
     // simulate!(sys, ::Langevin, n_steps) (simulators.jl:1099-1220) without constraints: per step the forces of the current
     // coordinates, ONE fused update launch (kick, half drift, O-step, half drift, wrap, Σ m v partials), the neighbour cadence.
     // ctr1 advances by one per step (:1190) from ctr1_0 + (first_step's offset), so chunked continuation reproduces one long run.
     void langevin_run(int64_t first_step, int64_t n_steps, double dt, double kT, double friction, int remove_cm_every, uint64_t key, uint64_t ctr1_0) override {
-        if (!held.state_set() || !held.params_set()) throw ApiError{MHIP_ERR_STATE, "set_atoms and set_state must be called before langevin_run"};
-        if (n_ghost > 0) throw ApiError{MHIP_ERR_STATE, "langevin_run is single-domain"};
-        if (thermo_on()) throw ApiError{MHIP_ERR_UNSUPPORTED, "the rescaling thermostats are a coupling of mhip_vv_run: unset the thermostat before mhip_langevin_run"};
+        admit(adm::LANGEVIN_RUN);      // (the rescaling thermostats are a coupling of mhip_vv_run)
         if (!(kT >= 0) || !(friction >= 0)) throw ApiError{MHIP_ERR_INVALID, "temperature and friction must be non-negative"};
         const int every = rebuild_every();
         lp.cur_dt = dt;
@@ -2886,7 +2868,6 @@ template <class T> class Engine final : public EngineBase {
         if (now) lists_after_set_state();
         if (held.stale()) {   // never built, or invalidated by new coordinates / exceptions: search now
             if (!now) return 0;
-            if (!held.state_set() || !held.params_set()) throw ApiError{MHIP_ERR_STATE, "no neighbour list: call set_atoms and set_state first"};
             flush_cm(); rebuild(last_build_step == std::numeric_limits<int64_t>::min() ? 0 : last_build_step);
         }
         if (now && lazy_single && (last_build_step != lp.last_prune_step || held.export_needs_search())) { flush_cm(); rebuild(last_build_step); }   // skipped rebuilds / moved coordinates: hand out the list of NOW
@@ -3063,14 +3044,7 @@ int32_t mhip_check_finite(mhip_ctx* ctx) { NEED_CTX(); return guard(ctx, [&] { c
 int32_t mhip_vv_run(mhip_ctx* ctx, int64_t first, int64_t n, double dt, int32_t cm) {
     NEED_CTX(); return guard(ctx, [&] { if (n < 0 || !(dt > 0)) throw mhip::ApiError{MHIP_ERR_INVALID, "n_steps must be >= 0 and dt > 0"}; ctx->e->vv_run(first, n, dt, cm); });
 }
-int32_t mhip_vv_init(mhip_ctx* ctx, int64_t first) {
-    NEED_CTX();
-    return guard(ctx, [&] {
-        if (ctx->e->constrained()) throw mhip::ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no constraints: use mhip_vv_run"};
-        if (ctx->e->has_sites()) throw mhip::ApiError{MHIP_ERR_UNSUPPORTED, "the split step (vv_init / vv_stage1 / vv_stage2) has no virtual sites: use mhip_vv_run"};
-        ctx->e->vv_init(first);
-    });
-}
+int32_t mhip_vv_init(mhip_ctx* ctx, int64_t first) { NEED_CTX(); return guard(ctx, [&] { ctx->e->vv_init(first); }); }
 int32_t mhip_vv_stage1(mhip_ctx* ctx, double dt) { NEED_CTX(); return guard(ctx, [&] { ctx->e->vv_stage1(dt); }); }
 int32_t mhip_vv_stage2(mhip_ctx* ctx, int64_t step_n, double dt) { NEED_CTX(); return guard(ctx, [&] { ctx->e->vv_stage2(step_n, dt); }); }
 int32_t mhip_rebuild(mhip_ctx* ctx, int64_t step_n) { NEED_CTX(); return guard(ctx, [&] { ctx->e->rebuild_now(step_n); }); }

@@ -350,62 +350,18 @@ def test_refusals(pkg):
 
 
 def test_refusals_with_halo_and_domain_plans(pkg):
-    """the halo entry points, mhip_set_halo_plan, mhip_set_domain and mhip_domain_run refuse a context with a thermostat set; mhip_set_thermostat refuses a
-    context that has a halo plan or a domain plan; the context is usable after every refusal"""
-    from molly_jl_amd import _lib
+    """the halo entry points, mhip_set_halo_plan, mhip_set_domain, mhip_halo_region with peers and mhip_domain_run refuse a context with a thermostat set;
+    mhip_set_thermostat refuses a context that has a halo plan, a domain plan or peers; the context is usable after every refusal (tests/admit_walk.py)"""
+    from tests import admit_walk
     L = pkg.lib()
-    case = fluid(257)
     ok = (TR.BERENDSEN, KB * 120.0, 0.1, 1, 3 * 257 - 3, 0, 0)
     off = (0, 0.0, 0.0, 1, 0, 0, 0)
 
-    def fresh():
-        s = case.system(pkg, np.float64)
-        s.push_state(velocities=True)
-        return s
-
-    def usable(s, first, n_applied):
-        assert L.mhip_vv_run(s._ctx, first, 2, 0.002, 1) == 0, L.mhip_last_error(s._ctx).decode()
-        assert info_of(pkg, s)[0] == n_applied
-    plan = _lib.HaloPlan()          # no rows, no peers: a valid (empty) plan
-    geom = _lib.DomainGeometry()    # one brick, periodic on every axis
-    for d in range(3):
-        geom.grid[d] = 1; geom.box[d] = float(case.box[d])
-    geom.rank = 0; geom.r_ghost = 0.0
-    done, reason = C.c_int64(0), C.c_int32(0)
-    counters = (C.c_int64 * 8)()
-    # (1) a thermostat is set: every ghosted / domain entry point refuses, and the coupled run goes on after each
-    s = fresh()
-    assert L.mhip_set_thermostat(s._ctx, *ok) == 0
-    step = 0
-    for what, call in [
-            ("mhip_set_halo_plan", lambda: L.mhip_set_halo_plan(s._ctx, C.byref(plan))),
-            ("mhip_set_domain", lambda: L.mhip_set_domain(s._ctx, C.byref(geom), None)),
-            ("mhip_domain_run", lambda: L.mhip_domain_run(s._ctx, step, 2, 0.002, 0, None, 0, C.byref(done), C.byref(reason), C.cast(counters, C.POINTER(C.c_int64)))),
-            ("mhip_vv_halo_start", lambda: L.mhip_vv_halo_start(s._ctx, 0.002)),
-            ("mhip_vv_halo_mid", lambda: L.mhip_vv_halo_mid(s._ctx, step + 1, 0.002, 0, None, 0)),
-            ("mhip_vv_halo_begin", lambda: L.mhip_vv_halo_begin(s._ctx, 0.002, None, None, 0, None)),
-            ("mhip_vv_halo_end", lambda: L.mhip_vv_halo_end(s._ctx, step + 1, 0.002, 0, 0, None, None)),
-            ("mhip_vv_halo_end_parts", lambda: L.mhip_vv_halo_end_parts(s._ctx, step + 1, 0.002, 0, 0, None, None, 0))]:
-        assert call() == ERR_UNSUPPORTED, what
-        usable(s, step, 2)      # (simulate-style: the record counts the applications of the run just made)
-        step += 2
-        assert L.mhip_set_thermostat(s._ctx, *ok) == 0      # "since set": the record starts again
-    # (2) a plan is there first: mhip_set_thermostat refuses, the context steps uncoupled, and takes the thermostat once the plan is gone
-    s = fresh()
-    assert L.mhip_set_halo_plan(s._ctx, C.byref(plan)) == 0
-    assert L.mhip_set_thermostat(s._ctx, *ok) == ERR_UNSUPPORTED
-    assert L.mhip_set_thermostat(s._ctx, *off) == 0      # switching off is always allowed
-    assert L.mhip_vv_run(s._ctx, 0, 2, 0.002, 1) == 0
-    assert L.mhip_set_halo_plan(s._ctx, None) == 0
-    assert L.mhip_set_thermostat(s._ctx, *ok) == 0
-    usable(s, 2, 2)
-    s = fresh()
-    assert L.mhip_set_domain(s._ctx, C.byref(geom), None) == 0, L.mhip_last_error(s._ctx).decode()
-    assert L.mhip_set_thermostat(s._ctx, *ok) == ERR_UNSUPPORTED
-    assert L.mhip_vv_run(s._ctx, 0, 2, 0.002, 1) == 0
-    assert L.mhip_set_domain(s._ctx, None, None) == 0
-    assert L.mhip_set_thermostat(s._ctx, *ok) == 0
-    usable(s, 2, 2)
+    def after_run(s, on):
+        if on:      # (simulate-style: the record counts the applications of the run just made)
+            assert info_of(pkg, s)[0] == 2
+            assert L.mhip_set_thermostat(s._ctx, *ok) == 0      # "since set": the record starts again
+    admit_walk.walk(pkg, fluid(257), lambda s: L.mhip_set_thermostat(s._ctx, *ok), lambda s: L.mhip_set_thermostat(s._ctx, *off), after_run)
 
 
 # ---- physics, once ----------------------------------------------------------------------------------------------------------------------
