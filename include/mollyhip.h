@@ -274,6 +274,23 @@ int32_t mhip_check_finite(mhip_ctx* ctx);          /* check_nans, simulators.jl:
  * numbers the recomputation yields: same lists, same order).  MOLLYHIP_REUSE_RUN_FORCES=0 always recomputes. */
 int32_t mhip_vv_run(mhip_ctx* ctx, int64_t first_step, int64_t n_steps, double dt,
                     int32_t remove_cm_every);
+/* simulate!(sys, ::SteepestDescentMinimizer) (simulators.jl:183-271) on the coordinates the context holds, the loop and its decisions on the device:
+ *   place the sites, bring the lists up to date, E = potential energy, hn = step_size; then for step = first_step+1 … first_step+max_steps:
+ *   F = total force (pair + specific + general + constraint bonds, every site's force spread onto its parents and its row zeroed);
+ *   max_force = max ‖F_i‖; x_trial = wrap(x + (hn·F)/max_force), sites placed again; E_trial < E ? (E = E_trial, hn = 6·hn/5) : (x stays, hn = hn/5);
+ *   stop after the step if max_force < tol.  hn and the move are in the context's precision, the energies doubles summed pair + specific + general.
+ * A NaN energy rejects.  One deviation from the reference: max_force == 0 stops the loop as converged, without the division.
+ * constraint_bond_k > 0: every constrained pair of mhip_set_constraints (the centre–satellite pairs of a central cluster, all three sides of an angle
+ * cluster) is a harmonic bond k/2·(r − d)² for the duration of the call (constraints_to_bonds, constraints/constraints.jl:619-636); 0: the constraints
+ * are ignored (constraint_bond_constant = nothing); unused without constraints.  SHAKE is never applied.
+ * log4 (nullable): host doubles, 4·max_steps; per step taken E_trial, max_force, accepted (1/0), the hn it moved by.
+ * out8 (nullable): initial E, final E, the last max_force, the final hn, steps taken, accepted steps, rejected steps, converged (1/0).
+ * Velocities are untouched.  The forces kept for a continued run are void afterwards: the next mhip_vv_run recomputes them.  The host waits once per
+ * step, for one small pinned record; forces, trial coordinates and energies stay on the device.
+ * MHIP_ERR_INVALID: max_steps < 0, first_step < 0, step_size not positive and finite, tol NaN, constraint_bond_k negative or not finite.  Otherwise
+ * admitted and refused exactly as mhip_vv_run (a single domain: MHIP_ERR_STATE with ghost atoms or before mhip_set_atoms / mhip_set_state). */
+int32_t mhip_minimize(mhip_ctx* ctx, int64_t first_step, int64_t max_steps, double step_size, double tol,
+                      double constraint_bond_k, double* log4, double* out8);
 /* The same step split at the point where a multi-GPU host exchanges ghost coordinates:
  *   stage1: v += a dt/2; x += v dt; x = wrap(x)           (owned atoms)
  *   stage2: F = forces(x) [+ specific]; v += a' dt/2      (owned atoms; ghosts read-only)     */

@@ -123,3 +123,16 @@ function constraint_virial!(virial9::Vector{Float64}, parts18::Vector{Float64}, 
                    c.ptr, f, 0, dt, virial9, parts18, n_not_converged))
     return n_not_converged[]
 end
+
+# mhip_minimize: the steepest-descent loop of simulators.jl:183-271 on the coordinates the context holds, with its decisions taken on the device.
+# constraint_bond_k > 0 puts a harmonic bond k/2·(r − d)² on every constrained pair for the duration (constraints_to_bonds, constraints.jl:619-636), 0 ignores
+# the constraints.  log4 (4 × max_steps): per step taken E_trial, max_force, accepted, the hn it moved by.  Returns out8 = (initial E, final E, last max_force,
+# final hn, steps taken, accepted, rejected, converged).
+function minimize!(log4::Matrix{Float64}, c::HipContext; first_step::Integer=0, max_steps::Integer=1000, step_size::Float64=0.01, tol::Float64=1000.0,
+                   constraint_bond_k::Float64=500_000.0)
+    size(log4) == (4, max_steps) || error("libmollyhip: minimize! takes a 4 × max_steps log")
+    out8 = zeros(Float64, 8)
+    check(c, ccall((:mhip_minimize, libmollyhip), Int32, (Ptr{Cvoid}, Int64, Int64, Float64, Float64, Float64, Ptr{Float64}, Ptr{Float64}),
+                   c.ptr, first_step, max_steps, step_size, tol, constraint_bond_k, log4, out8))
+    return out8
+end

@@ -108,6 +108,7 @@ SIGNATURES = {
     "mhip_remove_cm": (_I32, [_P]),
     "mhip_check_finite": (_I32, [_P]),
     "mhip_vv_run": (_I32, [_P, _I64, _I64, _D, _I32]),
+    "mhip_minimize": (_I32, [_P, _I64, _I64, _D, _D, _D, C.POINTER(_D), C.POINTER(_D)]),
     "mhip_vv_init": (_I32, [_P, _I64]),
     "mhip_vv_stage1": (_I32, [_P, _D]),
     "mhip_vv_stage2": (_I32, [_P, _I64, _D]),

@@ -260,11 +260,15 @@ class VelocityVerlet:
 @dataclass
 class SteepestDescentMinimizer:
     """SteepestDescentMinimizer(; step_size=0.01 nm, max_steps=1000, tol=1000 kJ mol⁻¹ nm⁻¹) (simulators.jl:112-135): x += hn · F / max|F|, the step taken when
-    the potential energy falls (hn · 6/5) and taken back otherwise (hn / 5), until max|F| < tol"""
+    the potential energy falls (hn · 6/5) and taken back otherwise (hn / 5), until max|F| < tol.
+    engine_loop=True runs the loop in the engine (mhip_minimize), which also takes constrained Systems — every constrained pair a harmonic bond of
+    constraint_bond_constant [kJ mol⁻¹ nm⁻²] for the duration, None: the constraints ignored (constraints_to_bonds, constraints.jl:619-636) — and virtual sites"""
     step_size: float = 0.01
     max_steps: int = 1000
     tol: float = 1000.0
     log_stream: object = None
+    constraint_bond_constant: object = 500_000.0
+    engine_loop: bool = False
 
 
 @dataclass
@@ -888,6 +892,22 @@ def _minimize(sys, sim, init_step=0):
     return sys
 
 
+def _minimize_engine(sys, sim, init_step=0):
+    """The same loop inside the engine (mhip_minimize): the state goes over once and comes back once, the log lines are printed from the call's records"""
+    k = 0.0 if sim.constraint_bond_constant is None else float(sim.constraint_bond_constant)
+    n = int(sim.max_steps)
+    log4 = np.zeros((max(n, 1), 4), np.float64); out8 = np.zeros(8, np.float64)
+    sys.push_state(velocities=True)
+    sys._check(_lib.lib().mhip_minimize(sys._ctx, int(init_step), n, float(sim.step_size), float(sim.tol), k,
+                                        log4.ctypes.data_as(C.POINTER(C.c_double)), out8.ctypes.data_as(C.POINTER(C.c_double))))
+    sys.pull_state()
+    if sim.log_stream is not None:
+        print("Step", init_step, "- potential energy", out8[0], "- max force N/A - N/A", file=sim.log_stream)
+        for s in range(int(out8[4])):
+            print("Step", init_step + 1 + s, "- potential energy", log4[s, 0], "- max force", sys.dtype.type(log4[s, 1]), "-", "accepted" if log4[s, 2] else "rejected", file=sim.log_stream)
+    return sys
+
+
 def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
     """simulate!(sys, sim, n_steps; init_step, rng) for VelocityVerlet (simulators.jl:547-668) and Langevin (:1099-1220), with
     coupling nothing, AndersenThermostat, MonteCarloBarostat or a tuple of the two; VelocityVerlet also takes ImmediateThermostat, BerendsenThermostat and
@@ -895,6 +915,10 @@ def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
     multiples of barostat.n_steps, where apply_coupling! runs on the host side of the boundary with the engine's potential energies (the README's GPU
     example: Langevin + MonteCarloBarostat).  Coordinates and velocities come back when the call returns.  rng: a numpy Generator or a seed; as in the
     reference it supplies the Philox key / counter words and the barostat's uniform numbers."""
+    if isinstance(sim, SteepestDescentMinimizer) and sim.engine_loop:
+        if init_step < 0:
+            raise ValueError("init_step must be non-negative")
+        return _minimize_engine(sys, sim, init_step)
     if isinstance(sim, SteepestDescentMinimizer):
         sys._refuse_constrained("minimization")
         sys._refuse_sites("minimization")

@@ -17,6 +17,7 @@
 #include "stochastic.h"
 #include "constraints.h"
 #include "virtual_sites.h"
+#include "minimize.h"
 #include "pme.h"
 #include "step_fused.h"
 #include "hilbert.h"
@@ -112,6 +113,7 @@ struct EngineBase {
     virtual void distribute_forces(void*, int) = 0;
     virtual void virtual_site_info(int64_t*) = 0;
     virtual void domain_export(int64_t*, void*) = 0;
+    virtual void minimize(int64_t, int64_t, double, double, double, double*, double*) = 0;
 };
 
 // hipEvent stage timers (only active while profiling is on)
@@ -266,11 +268,11 @@ template <class T> class Engine final : public EngineBase {
         for (int k = 0; k < adm::N_MODES; ++k) m |= (f[k] ? 1u : 0u) << k;
         return m;
     }
-    void admit(adm::Entry e, uint32_t granted = 0) const {
+    void admit(adm::Entry e, uint32_t granted = 0, const char* name = nullptr) const {      // name: a call that shares another's row under its own name
         static_assert((int)adm::Code::N_CODES == 3, "admit.h answers OK, UNSUPPORTED or STATE: one code of mollyhip.h each");
         static const int32_t code_of[] = {MHIP_OK, MHIP_ERR_UNSUPPORTED, MHIP_ERR_STATE};
         const adm::Verdict v = adm::admit(e, modes() | granted);
-        if (v.code != adm::Code::OK) throw ApiError{code_of[(int)v.code], std::string(adm::row(e).name) + " " + v.why};
+        if (v.code != adm::Code::OK) throw ApiError{code_of[(int)v.code], std::string(name ? name : adm::row(e).name) + " " + v.why};
     }
     bool minimg = false; int64_t n_set_state_refresh = 0;
     int64_t last_build_step = std::numeric_limits<int64_t>::min();
@@ -1674,6 +1676,12 @@ template <class T> class Engine final : public EngineBase {
         return pme.on() ? pme_energy() : 0.0;
     }
     double pme_energy() {
+        const int nb = pme_energy_parts();
+        return 0.5 * read_sum(nb) + pme_energy_const();   // ewald.jl:917-928
+    }
+    double pme_energy_const() const { return pme.self_factor * pc_abs2_sum + pme.charge_factor * pc_sum * pc_sum; }
+    // the reciprocal-space energy as conv_blocks() partials in red_part (returned: their count); Σq, Σq² read back once per set of charges
+    int pme_energy_parts() {
         admit(adm::FORCE_PASS);
         if (!pc_valid) {   // Σq and Σq² (ewald.jl:917-924) from the charges kept in pos.w
             std::vector<T4> hp(n_owned);
@@ -1686,7 +1694,7 @@ template <class T> class Engine final : public EngineBase {
         const int nb = pme.conv_blocks();
         red_part.reserve(7 * (size_t)nb);
         pme.run(stream, n_owned, pos[cur].p, (T4*)nullptr, red_part.p);
-        return 0.5 * read_sum(nb) + pme.self_factor * pc_abs2_sum + pme.charge_factor * pc_sum * pc_sum;   // ewald.jl:917-928
+        return nb;
     }
 
     double kinetic_energy() override {
@@ -2769,6 +2777,120 @@ template <class T> class Engine final : public EngineBase {
         launch_con_step<T>(stream, nb, mode, C, A, G, th ? &X : nullptr);
         MHIP_HIP(hipGetLastError());
     }
+    // ---- steepest-descent minimisation (minimize.h): simulate!(sys, ::SteepestDescentMinimizer), simulators.jl:183-271 --------------------------
+    // The loop runs here, its decisions on the device: per step the host waits once, for the pinned record k_min_publish writes (max ‖F‖, E_trial, accepted,
+    // the next hn, the displacement of the coordinates that stand against the lists' snapshots).  Constraints are never solved: with cbk > 0 every constrained
+    // pair is a harmonic bond k/2·(r − d)² for the duration (constraints_to_bonds, constraints/constraints.jl:619-636), with cbk == 0 they are ignored.
+    // Lists: the displacement of the coordinates that stand is measured by each step's last grid launch; a trial moves every atom by at most hn (the sites: by
+    // at most hn·Σ|w|; an OutOfPlaneSite has no such bound, so the lists of a System that has one are searched anew for every trial), hence measured + bound
+    // decides, before the trial energy, whether the lists are pruned or searched again: every force and energy is evaluated on lists exact for its coordinates.
+    DBuf<double> min_rec, min_sums; Pinned<double> h_min; DBuf<T> min_part; DBuf<float> min_dpart; DBuf<T4> min_keep;
+    bool min_dirty = false;      // lists without a skin: the coordinates have changed since the last search
+    // the lists cover coordinates that lie within d_in / d_out of the inner (or only) / the outer list's snapshot — or are made to
+    void min_cover(int64_t step, double d_in, double d_out) {
+        if (held.stale()) { rebuild(step); min_dirty = false; return; }
+        if (!(dual || lazy_single)) { if (min_dirty) rebuild(step); min_dirty = false; return; }
+        if (dual) {
+            if (held.inner_valid() && ListPolicy::covered(d_in, 0.0, lp.skin_in)) return;      // (the passes walk the inner list: the outer one is asked only for a prune)
+            if (!lp.prune_stands(d_out)) { rebuild(step); return; }
+            held.prune_wanted();                                                               // the next force pass prunes; until then the passes walk the outer list
+        } else if (!ListPolicy::covered(d_in, 0.0, lp.skin)) rebuild(step);
+    }
+    MinBonds<T> min_bonds(double cbk) const {
+        MinBonds<T> B{};
+        B.atoms = con_atoms.p; B.d = con_d.p; B.inv = inv.p; for (int k = 0; k < 4; ++k) B.end[k] = con.end[k];
+        B.k = T(cbk);
+        return B;
+    }
+    // the energy passes at the coordinates held, their sums left in min_sums; what the total is made of
+    MinParts min_energy(bool bonds, double cbk) {
+        MinParts P{};
+        energy_pass();
+        launch_min_sum(stream, n_blocks, red_part.p, min_sums.p + MS_PAIR); P.pair = 1;
+        if (const int nb = bonded.launch_energy(stream, G, I, pos[cur].p, inv.p, red_part)) { launch_min_sum(stream, nb, red_part.p, min_sums.p + MS_SPEC); P.spec = 1; }
+        if (pme.on()) {
+            const int nb = pme_energy_parts();
+            launch_min_sum(stream, nb, red_part.p, min_sums.p + MS_GEN); P.gen = 1; P.gen_const = pme_energy_const();
+        }
+        if (bonds) {
+            red_part.reserve(MIN_MAX_BLOCKS);
+            const int nb = launch_min_cbonds<T>(stream, min_bonds(cbk), pos[cur].p, (T4*)nullptr, red_part.p, true, G);
+            launch_min_sum(stream, nb, red_part.p, min_sums.p + MS_CBOND); P.cbond = 1;
+        }
+        MHIP_HIP(hipGetLastError());
+        return P;
+    }
+    // the step's last launches and its one wait: restore (a rejected step), measure, publish → the record in h_min
+    void min_settle_wait(bool restore) {
+        const T4* snap_out = dual && !held.stale() ? (const T4*)pos_snap.p : nullptr;
+        const T4* snap_in = !held.stale() && (dual ? held.inner_valid() : lazy_single) ? (const T4*)pos_snap_in.p : nullptr;
+        const int nb = launch_min_settle<T>(stream, n_owned, pos[cur].p, orig[cur].p, min_keep.p, min_rec.p, restore, snap_in, snap_out, min_dpart.p, G);
+        launch_min_publish(stream, nb, min_dpart.p, min_rec.p, h_min);
+        MHIP_HIP(hipGetLastError());
+        MHIP_HIP(hipStreamSynchronize(stream));
+    }
+    void minimize(int64_t first_step, int64_t max_steps, double step_size, double tol, double cbk, double* log4, double* out8) override {
+        admit(adm::VV_RUN, 0, "mhip_minimize");      // a step loop on a single domain that honours constraints and sites: the row of mhip_vv_run
+        lp.cur_dt = 0;      // no time step to bound a drift with
+        flush_cm();
+        const bool bonds = con_on && cbk > 0 && con.end[CK_ANGLE] > 0;
+        min_rec.reserve(MR_N); min_sums.reserve(MS_N); h_min.make(MR_N); min_part.reserve(MIN_MAX_BLOCKS); min_dpart.reserve(2 * MIN_MAX_BLOCKS); min_keep.reserve(cap);
+        // how far a site can move when each of its parents moves by at most 1: Σ|w| of an average; unbounded for an out-of-plane site
+        double site_factor = 1.0;
+        if (vs_on) {
+            if (sites.n_type[3] > 0) site_factor = INFINITY;
+            else for (int64_t k = 0; k < sites.n; ++k) {
+                const double* w = sites.w.data() + 6 * k;
+                if (sites.type[k] == VS_TWO_AVG) site_factor = std::max(site_factor, std::fabs(w[0]) + std::fabs(w[1]));
+                if (sites.type[k] == VS_THREE_AVG) site_factor = std::max(site_factor, std::fabs(w[0]) + std::fabs(w[1]) + std::fabs(w[2]));
+            }
+        }
+        if (vs_on) place_sites();                                                  // simulators.jl:215 (the coordinates held are wrapped: set_state and every integrator wrap)
+        held.run_begins();
+        ensure_built(first_step);                                                  // :218
+        const MinParts P0 = min_energy(bonds, cbk);                                // :219
+        launch_min_decide<T>(stream, min_rec.p, min_sums.p, P0, true, step_size);
+        min_settle_wait(false);
+        double d_in = std::sqrt(h_min[MR_DISP_IN2]), d_out = std::sqrt(h_min[MR_DISP_OUT2]);
+        double hn = h_min[MR_HN], max_force = 0;
+        int64_t taken = 0; bool converged = false;
+        // a prune or a search on the way took new snapshots at the coordinates of the moment
+        auto retaken = [&](int64_t o0, int64_t f0) { if (n_outer != o0) d_in = d_out = 0; else if (n_filters != f0) d_in = 0; };
+        for (int64_t step = first_step + 1; step <= first_step + max_steps; ++step) {
+            int64_t o0 = n_outer, f0 = n_filters;
+            min_cover(step, d_in, d_out);
+            step_forces(step);                                                     // :226
+            fold_side_forces();
+            retaken(o0, f0);
+            if (bonds) launch_min_cbonds<T>(stream, min_bonds(cbk), pos[cur].p, frc[cur].p, (double*)nullptr, false, G);
+            if (vs_on) launch_min_spread<T>(stream, vs_params(), (const T4*)pos[cur].p, frc[cur].p, G);      // distribute_forces!
+            const int nb = launch_min_maxf<T>(stream, n_owned, frc[cur].p, min_part.p);                       // :227
+            launch_min_move<T>(stream, n_owned, pos[cur].p, frc[cur].p, orig[cur].p, min_keep.p, min_part.p, nb, min_rec.p, G);      // :229-233
+            MHIP_HIP(hipGetLastError());
+            drifted(); min_dirty = true;
+            if (vs_on) { launch_vs_place<T>(stream, vs_params(), pos[cur].p, G, nullptr); vs_place_due = false; }      // :240
+            const double bound = hn * site_factor;
+            o0 = n_outer; f0 = n_filters;
+            min_cover(step, d_in + bound, d_out + bound);
+            retaken(o0, f0);
+            const MinParts P = min_energy(bonds, cbk);                             // :243
+            launch_min_decide<T>(stream, min_rec.p, min_sums.p, P, false, step_size);      // :245-263
+            min_settle_wait(true);
+            d_in = std::sqrt(h_min[MR_DISP_IN2]); d_out = std::sqrt(h_min[MR_DISP_OUT2]);
+            if (h_min[MR_ACCEPTED] == 0) min_dirty = true;      // (back where the step began)
+            hn = h_min[MR_HN]; max_force = h_min[MR_MAXF];
+            if (log4) { double* row = log4 + 4 * taken; row[0] = h_min[MR_E_TRIAL]; row[1] = max_force; row[2] = h_min[MR_ACCEPTED]; row[3] = h_min[MR_HN_USED]; }
+            ++taken;
+            if (max_force < tol || max_force == 0) { converged = true; break; }      // :264 (max_force == 0: the reference would divide by it)
+        }
+        min_cover(first_step + taken, d_in, d_out);      // the lists are what the record says they are, for the coordinates that stand
+        MHIP_HIP(hipStreamSynchronize(stream));
+        if (out8) {
+            out8[0] = h_min[MR_E0]; out8[1] = h_min[MR_E]; out8[2] = max_force; out8[3] = hn;
+            out8[4] = (double)taken; out8[5] = h_min[MR_N_ACC]; out8[6] = h_min[MR_N_REJ]; out8[7] = converged ? 1.0 : 0.0;
+        }
+    }
+
     // ---- stochastic dynamics (kernels in stochastic.hip) ------------------------------------------------------
     StochP<T> stoch_params(double kT, uint64_t key, uint64_t ctr1) const {
         StochP<T> P{};
@@ -3048,6 +3170,16 @@ int32_t mhip_vv_init(mhip_ctx* ctx, int64_t first) { NEED_CTX(); return guard(ct
 int32_t mhip_vv_stage1(mhip_ctx* ctx, double dt) { NEED_CTX(); return guard(ctx, [&] { ctx->e->vv_stage1(dt); }); }
 int32_t mhip_vv_stage2(mhip_ctx* ctx, int64_t step_n, double dt) { NEED_CTX(); return guard(ctx, [&] { ctx->e->vv_stage2(step_n, dt); }); }
 int32_t mhip_rebuild(mhip_ctx* ctx, int64_t step_n) { NEED_CTX(); return guard(ctx, [&] { ctx->e->rebuild_now(step_n); }); }
+int32_t mhip_minimize(mhip_ctx* ctx, int64_t first, int64_t max_steps, double step_size, double tol, double cbk, double* log4, double* out8) {
+    NEED_CTX();
+    return guard(ctx, [&] {
+        if (max_steps < 0 || first < 0) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_minimize: first_step and max_steps must be >= 0"};
+        if (!(step_size > 0) || !std::isfinite(step_size)) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_minimize: step_size must be positive and finite"};
+        if (std::isnan(tol)) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_minimize: tol is NaN"};
+        if (!(cbk >= 0) || !std::isfinite(cbk)) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_minimize: constraint_bond_k must be finite and >= 0"};
+        ctx->e->minimize(first, max_steps, step_size, tol, cbk, log4, out8);
+    });
+}
 int32_t mhip_export_neighbors(mhip_ctx* ctx, int32_t* i, int32_t* j, uint8_t* sp, int64_t capacity, int64_t* n_out) {
     NEED_CTX();
     return guard(ctx, [&] {
