@@ -4,7 +4,7 @@
 #include <algorithm>
 #include <numeric>
 
-#include "kernels.h"
+#include "integrate.h"
 #include "philox.h"
 
 namespace mhip {
@@ -534,23 +534,8 @@ __device__ __forceinline__ void con_step_body(const ConP<T>& C, const ConStep<T>
         if (mi > 0) atomicMax(&C.stat[1], (unsigned long long)mi);
         if (nf > 0) atomicAdd(&C.stat[0], (unsigned long long)nf);
     }
-    if (A.trk_part) {
-        __shared__ float sht[3][16];
-        const float da = wave_max(acc.da), db = wave_max(acc.db), v2 = wave_max(acc.v2);
-        if ((threadIdx.x & 63) == 0) { sht[0][threadIdx.x >> 6] = da; sht[1][threadIdx.x >> 6] = db; sht[2][threadIdx.x >> 6] = v2; }
-        __syncthreads();
-        if (threadIdx.x < 3) { float m = 0.f; for (int q = 0; q < (int)(blockDim.x >> 6); ++q) m = fmaxf(m, sht[threadIdx.x][q]); A.trk_part[threadIdx.x * gridDim.x + blockIdx.x] = m; }
-    }
-    if (A.cm_out) {
-        __shared__ double shm[4][4];
-        double px = acc.px, py = acc.py, pz = acc.pz, m = acc.m;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { px += __shfl_xor(px, o, 64); py += __shfl_xor(py, o, 64); pz += __shfl_xor(pz, o, 64); m += __shfl_xor(m, o, 64); }
-        const int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) { shm[w][0] = px; shm[w][1] = py; shm[w][2] = pz; shm[w][3] = m; }
-        __syncthreads();
-        if (threadIdx.x < 4) { double a = 0; for (int q = 0; q < (int)(blockDim.x >> 6); ++q) a += shm[q][threadIdx.x]; A.cm_out[4 * (int64_t)blockIdx.x + threadIdx.x] = a; }
-    }
+    if (A.trk_part) block_trk_write(acc.da, acc.db, acc.v2, A.trk_part);
+    if (A.cm_out) block_cm_write(acc.px, acc.py, acc.pz, acc.m, A.cm_out);
     if constexpr (TH && MODE == 2) thermo_write_partial(acc.mv2, thermo_noise_share<T>(X.th), X.th_out);
 }
 

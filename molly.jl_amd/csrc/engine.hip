@@ -22,6 +22,7 @@
 #include "step_fused.h"
 #include "hilbert.h"
 #include "kernels.h"
+#include "integrate.h"
 #include "list_policy.h"
 #include "held.h"
 #include "admit.h"

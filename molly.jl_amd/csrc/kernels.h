@@ -16,7 +16,6 @@
 #include "physics.h"
 #include "halo_xfer.h"
 #include "philox.h"
-#include "thermostat_step.h"
 
 namespace mhip {
 
@@ -163,6 +162,12 @@ template <class T> __device__ inline void disp_image(T& ex, T& ey, T& ez, const 
         if (G.periodic[1]) ey -= G.L[1] * M<T>::rint(ey * G.invL[1]);
         if (G.periodic[2]) ez -= G.L[2] * M<T>::rint(ez * G.invL[2]);
     }
+}
+// |(x, y, z) − q|² of that displacement, as the validity checks of the pair lists compare it; the caller keeps its own maximum
+template <class T, class V4> __device__ inline float disp2_from(T x, T y, T z, const V4 q, const GridP<T>& G) {
+    T ex = x - q.x, ey = y - q.y, ez = z - q.z;
+    disp_image(ex, ey, ez, G);
+    return (float)(ex * ex + ey * ey + ez * ez);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -980,16 +985,9 @@ __global__ void k_max_disp(int64_t n, const typename Vec<T>::T4* __restrict__ po
                            const typename Vec<T>::T4* __restrict__ snap_b = nullptr, unsigned int* out_b = nullptr) {   // (a second snapshot in the same pass)
     float d2 = 0.f, v2 = 0.f, b2 = 0.f;
     for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
-        auto p = pos[s]; auto q = snap[s];
-        T ex = p.x - q.x, ey = p.y - q.y, ez = p.z - q.z;
-        disp_image(ex, ey, ez, G);
-        d2 = fmaxf(d2, (float)(ex * ex + ey * ey + ez * ez));
-        if (snap_b) {
-            q = snap_b[s];
-            ex = p.x - q.x; ey = p.y - q.y; ez = p.z - q.z;
-            disp_image(ex, ey, ez, G);
-            b2 = fmaxf(b2, (float)(ex * ex + ey * ey + ez * ez));
-        }
+        const auto p = pos[s];
+        d2 = fmaxf(d2, disp2_from(p.x, p.y, p.z, snap[s], G));
+        if (snap_b) b2 = fmaxf(b2, disp2_from(p.x, p.y, p.z, snap_b[s], G));
         if (vel && s < n_vel) { auto v = vel[s]; v2 = fmaxf(v2, (float)(v.x * v.x + v.y * v.y + v.z * v.z)); }
     }
     d2 = wave_max(d2); v2 = wave_max(v2); b2 = wave_max(b2);
@@ -1167,6 +1165,21 @@ __global__ void __launch_bounds__(BlockLimits<T>::max_threads) k_filter(FilterAr
 // epilogue of k_forces go through these two helpers, so a run cut into chunks repeats the uncut run bit for bit (test/simulation.jl:16-57).
 template <class T> __device__ inline T accel_of(T f, T m) { return m == T(0) ? T(0) : f / m; }
 template <class T> __device__ inline T step_add(T x, T rate, T h) { return M<T>::add(x, M<T>::mul(rate, h)); }
+// The per-atom pieces that the opening and closing kernels of the integrator stage share (integrate.h, stochastic.hip): a lone kick (the first of an opening
+// step, the last of a run) and the drift (:602; the caller wraps); the velocity's share of a remove_CM_motion! applied one launch late.  The bodies that do a
+// middle step — half kick computed once and added twice, x −= v_cm·dt — write these operations out (vv_mid_body, con_item, k_gather_collect_vv, the STEP epilogue).
+template <class T, class V4> __device__ inline void lone_kick(V4& v, const V4& f, T dt2) { v.x = step_add(v.x, accel_of(f.x, v.w), dt2); v.y = step_add(v.y, accel_of(f.y, v.w), dt2); v.z = step_add(v.z, accel_of(f.z, v.w), dt2); }
+template <class T, class V4> __device__ inline void drift(V4& p, const V4& v, T dt) { p.x = step_add(p.x, v.x, dt); p.y = step_add(p.y, v.y, dt); p.z = step_add(p.z, v.z, dt); }
+template <class T, class V4> __device__ inline void cm_remove(V4& v, const T* vc) { v.x -= vc[0]; v.y -= vc[1]; v.z -= vc[2]; }
+// Every re-sum of the per-block Σ m v partials {Px, Py, Pz, M} starts here: a lane adds the partials threadIdx.x, threadIdx.x + blockDim.x, … in that order,
+// then the wave's butterfly.  What is left to the caller is the sum over its waves, in wave order.  (block_vcm and k_cm_finalize of integrate.h, k_halo_pack;
+// step_cm_publish and cm_finalize_in_block write the same lines out: through the call k_forces came out with other registers, and its stream is held fixed.)
+[[maybe_unused]] static __device__ inline void cm_partials_wave_sum(const double* __restrict__ part, int n_part, double (&a)[4]) {
+    for (int c = 0; c < 4; ++c) a[c] = 0;
+    for (int q = threadIdx.x; q < n_part; q += blockDim.x) { const double* p = part + 4 * (int64_t)q; a[0] += p[0]; a[1] += p[1]; a[2] += p[2]; a[3] += p[3]; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) for (int c = 0; c < 4; ++c) a[c] += __shfl_xor(a[c], o, 64);
+}
 
 // ---- the fused step of a ghosted sub-domain (k_forces STEP + HALO, fp32 one-type fluids inside mhip_domain_run) --------------------------------------------
 // ONE launch per MD step: the workgroups of blocks whose tile holds a ghost wait (bounded) for the peers' sequence words in their own prologue and stage the ghosts
@@ -1867,7 +1880,7 @@ k_forces(ForceArgs<T> A) {
         if (tid < A.JS * NWB) A.rows_dst[b * A.JS * NWB + tid] = l_wmax[tid];
         if (tid == 0) A.tile_cnt_dst[b] = n_new;
         float d2 = 0.f;
-        if (valid && js == 0) {
+        if (valid && js == 0) {      // (disp2_from written out: the instruction stream of this kernel is held fixed)
             T4 q = A.pos_snap[si];
             T ex = pi_raw.x - q.x, ey = pi_raw.y - q.y, ez = pi_raw.z - q.z;
             disp_image(ex, ey, ez, G);
@@ -1947,6 +1960,8 @@ k_forces(ForceArgs<T> A) {
                 langevin_atom<T>(v, p, f4, A.S, (uint64_t)A.orig[se] + 1, G);
                 if (A.cm_out) { px = (double)v.x * v.w; py = (double)v.y * v.w; pz = (double)v.z * v.w; pm = v.w; }
             } else {
+            // (written out, not through lone_kick / drift / cm_remove / disp2_from: with helpers the compiler orders the operands of the adds differently and
+            // fuses another product of |v|², and the instruction stream of this kernel is held fixed)
             const T kx = M<T>::mul(accel_of(fx, v.w), A.dt2), ky = M<T>::mul(accel_of(fy, v.w), A.dt2), kz = M<T>::mul(accel_of(fz, v.w), A.dt2);
             v.x = M<T>::add(v.x, kx); v.y = M<T>::add(v.y, ky); v.z = M<T>::add(v.z, kz);   // :616, v_n before this step's CM removal
             if (A.cm_out) { px = (double)v.x * v.w; py = (double)v.y * v.w; pz = (double)v.z * v.w; pm = v.w; }
@@ -2087,327 +2102,6 @@ __global__ void k_export_nl(int n_blocks, int BI, int JS, int T_cap, int R_cap, 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// velocity Verlet (simulators.jl:589-629), owned atoms, sorted order.  vel.w carries the mass.
-// v_cm = Σ(m v) / Σ m from the per-block partials of k_vv2, re-summed by EVERY block in the same fixed order (n_part <= 1024,
-// 32 KB of L2 reads per block): no separate finalize launch between the second kick and the next first kick.
-template <class T>
-__device__ inline void block_vcm(const double* __restrict__ part, int n_part, T* vcm3) {
-    __shared__ double sh_cm[4][4];
-    double a[4] = {0, 0, 0, 0};
-    for (int q = threadIdx.x; q < n_part; q += blockDim.x) { const double* p = part + 4 * (int64_t)q; a[0] += p[0]; a[1] += p[1]; a[2] += p[2]; a[3] += p[3]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) for (int c = 0; c < 4; ++c) a[c] += __shfl_xor(a[c], o, 64);
-    if ((threadIdx.x & 63) == 0) for (int c = 0; c < 4; ++c) sh_cm[threadIdx.x >> 6][c] = a[c];
-    __syncthreads();
-    double t[4] = {0, 0, 0, 0};
-    for (int q = 0; q < (int)(blockDim.x >> 6); ++q) for (int c = 0; c < 4; ++c) t[c] += sh_cm[q][c];
-    for (int c = 0; c < 3; ++c) vcm3[c] = (T)(t[c] / t[3]);
-}
-
-// The integrator's arithmetic is the reference's, operation by operation (no fused multiply-add, a true division): a = f / m with 0 for
-// massless atoms (calc_accels, force.jl:17), v += a·dt/2 (simulators.jl:594, 616), x += v·dt (:602).  Every kernel below goes through
-// these two helpers, so a run cut into chunks repeats the uncut run bit for bit (test/simulation.jl:16-57).
-// (accel_of / step_add are defined in front of k_forces, whose STEP variants integrate in their epilogue)
-
-template <class T>
-__global__ void k_vv1(int64_t n, typename Vec<T>::T4* pos, typename Vec<T>::T4* vel, const typename Vec<T>::T4* __restrict__ frc,
-                      T dt, T dt2, const T* __restrict__ vcm, const double* __restrict__ cm_part, int n_cm_part, GridP<T> G) {
-    T vc[3] = {T(0), T(0), T(0)};
-    const bool sub = vcm != nullptr || cm_part != nullptr;
-    if (cm_part) block_vcm<T>(cm_part, n_cm_part, vc);
-    else if (vcm) { vc[0] = vcm[0]; vc[1] = vcm[1]; vc[2] = vcm[2]; }
-    for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
-        auto v = vel[s]; auto p = pos[s]; auto f = frc[s];
-        if (sub) { v.x -= vc[0]; v.y -= vc[1]; v.z -= vc[2]; }                // deferred remove_CM_motion!
-        v.x = step_add(v.x, accel_of(f.x, v.w), dt2); v.y = step_add(v.y, accel_of(f.y, v.w), dt2); v.z = step_add(v.z, accel_of(f.z, v.w), dt2);   // :594
-        p.x = step_add(p.x, v.x, dt); p.y = step_add(p.y, v.y, dt); p.z = step_add(p.z, v.z, dt);   // :602
-        wrap_point(p.x, p.y, p.z, G);                                          // :609
-        vel[s] = v; pos[s] = p;
-    }
-}
-
-// fa (nullable): a second force array — the bonded sums + reciprocal-space forces of a small system's fused launches (step_fused.h) —
-// folded in here; the total is written back so that the next first kick sees it
-template <class T, bool CM>
-__global__ void k_vv2(int64_t n, typename Vec<T>::T4* vel, typename Vec<T>::T4* frc, T dt2, double* cm_part,
-                      const typename Vec<T>::T4* __restrict__ fa) {
-    double px = 0, py = 0, pz = 0, m = 0;
-    for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
-        auto v = vel[s]; auto f = frc[s];
-        if (fa) { const auto g = fa[s]; f.x += g.x; f.y += g.y; f.z += g.z; }
-        if (fa) frc[s] = f;
-        v.x = step_add(v.x, accel_of(f.x, v.w), dt2); v.y = step_add(v.y, accel_of(f.y, v.w), dt2); v.z = step_add(v.z, accel_of(f.z, v.w), dt2);   // :616
-        vel[s] = v;
-        if constexpr (CM) { px += (double)v.x * v.w; py += (double)v.y * v.w; pz += (double)v.z * v.w; m += v.w; }
-    }
-    if constexpr (CM) {
-        __shared__ double sh[4][4];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { px += __shfl_xor(px, o, 64); py += __shfl_xor(py, o, 64); pz += __shfl_xor(pz, o, 64); m += __shfl_xor(m, o, 64); }
-        int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) { sh[w][0] = px; sh[w][1] = py; sh[w][2] = pz; sh[w][3] = m; }
-        __syncthreads();
-        if (threadIdx.x < 4) { double a = 0; for (int q = 0; q < (int)(blockDim.x >> 6); ++q) a += sh[q][threadIdx.x]; cm_part[4 * (int64_t)blockIdx.x + threadIdx.x] = a; }
-    }
-}
-
-// Second kick of step n and first kick + drift of step n+1 in ONE pass over the atoms (vv_run, single domain): halves the integrator's
-// launches and its HBM traffic (48 B read + 32 B written per fp32 atom instead of 80 + 48).  remove_CM_motion! sits between the two
-// kicks and needs Σ m v of ALL atoms, so it is applied one kernel late: this launch accumulates the partials of Σ m v_n (before the
-// removal), carries on with the unshifted velocity, and the NEXT launch subtracts v_cm from the velocity it finds and v_cm·dt from
-// the position that was drifted with it.  The forces in between saw every atom translated by the same v_cm·dt (≈ 1e-11 nm): they are
-// translation invariant.  LAST: stop after the second kick (the run's final step), leaving v_n and x_n for the caller.
-// TH (with LAST: the close launch of a step on which a rescaling thermostat applies, thermostat_step.h): one more per-block output, th_out =
-// {Σ m|v|² of the velocities as stored, this block's share of the CSVR noise}.  The body is shared by two kernels: k_vv_mid, whose arguments and code
-// are what they were, and k_vv_close, which carries the thermostat's.
-template <class T, bool CM, bool LAST, bool TH>
-__device__ __forceinline__ void vv_mid_body(int64_t n, typename Vec<T>::T4* pos, typename Vec<T>::T4* vel, const typename Vec<T>::T4* __restrict__ fr, T dt, T dt2,
-                                            const double* __restrict__ cm_in, int n_cm_in, double* cm_out,
-                                            const typename Vec<T>::T4* __restrict__ fa, const GridP<T>& G,
-                                            const typename Vec<T>::T4* __restrict__ snap_a, const typename Vec<T>::T4* __restrict__ snap_b, float* trk_part,
-                                            const ThermoP& th, double* th_out) {
-    static_assert(!TH || LAST, "the thermostat's partials are taken by a launch that stops after the closing kick");
-    const typename Vec<T>::T4* __restrict__ frc = fr;
-    // trk_part (the validity check of the pair lists, taken where the new coordinates are made): per block the largest |x − snap_a|²,
-    // |x − snap_b|² and |v|² of what this launch leaves behind, trk_part[c·gridDim.x + block]
-    float v2m = 0.f, dam = 0.f, dbm = 0.f;
-    T vc[3] = {T(0), T(0), T(0)};
-    const bool sub = cm_in != nullptr;
-    // A lane's first atom is requested BEFORE the centre-of-mass partials are re-summed (32 KB of L2 reads, two barriers): the
-    // streaming part of the launch then starts behind that latency instead of after it.
-    using T4q = typename Vec<T>::T4;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, sn = s;
-    T4q vq = make4<T>(T(0), T(0), T(0), T(1)), fq = vq, pq = vq, gaq = vq;
-    auto fetch = [&](int64_t a) {
-        vq = vel[a]; fq = frc[a];
-        if (!LAST || sub) pq = pos[a];
-        if (fa) gaq = fa[a];
-    };
-    if (s < n) fetch(s);
-    if (sub) block_vcm<T>(cm_in, n_cm_in, vc);
-    const T sh[3] = {M<T>::mul(vc[0], dt), M<T>::mul(vc[1], dt), M<T>::mul(vc[2], dt)};
-    double px = 0, py = 0, pz = 0, m = 0;
-    [[maybe_unused]] double mv2 = 0;
-    for (; s < n; s = sn) {
-        sn = s + stride;
-        const auto v0 = vq, f0 = fq, p0 = pq, ga0 = gaq;
-        if (sn < n) fetch(sn);                                                 // the next atom's data travel while this one is integrated
-        auto v = v0; auto f = f0; auto p = p0;
-        if (fa) { f.x += ga0.x; f.y += ga0.y; f.z += ga0.z; }
-        if (sub) {                                                             // remove_CM_motion! of the previous step, one launch late
-            v.x -= vc[0]; v.y -= vc[1]; v.z -= vc[2];
-            p.x = M<T>::sub(p.x, sh[0]); p.y = M<T>::sub(p.y, sh[1]); p.z = M<T>::sub(p.z, sh[2]);
-        }
-        const T kx = M<T>::mul(accel_of(f.x, v.w), dt2), ky = M<T>::mul(accel_of(f.y, v.w), dt2), kz = M<T>::mul(accel_of(f.z, v.w), dt2);
-        v.x = M<T>::add(v.x, kx); v.y = M<T>::add(v.y, ky); v.z = M<T>::add(v.z, kz);   // :616, v_n before this step's CM removal
-        if constexpr (CM) { px += (double)v.x * v.w; py += (double)v.y * v.w; pz += (double)v.z * v.w; m += v.w; }
-        if constexpr (TH) thermo_accum<T>(v, mv2);
-        if constexpr (!LAST) {
-            v.x = M<T>::add(v.x, kx); v.y = M<T>::add(v.y, ky); v.z = M<T>::add(v.z, kz);   // :594 of the next step
-            p.x = step_add(p.x, v.x, dt); p.y = step_add(p.y, v.y, dt); p.z = step_add(p.z, v.z, dt);   // :602
-        }
-        if (!LAST || sub) {
-            wrap_point(p.x, p.y, p.z, G);                                      // :609
-            pos[s] = p;
-        }
-        if (LAST && fa) const_cast<typename Vec<T>::T4*>(frc)[s] = f;  // the total force of the last step stays readable
-        vel[s] = v;
-        if (trk_part) {
-            v2m = fmaxf(v2m, (float)(v.x * v.x + v.y * v.y + v.z * v.z));
-            auto q = snap_a[s];
-            T ex = p.x - q.x, ey = p.y - q.y, ez = p.z - q.z;
-            disp_image(ex, ey, ez, G);
-            dam = fmaxf(dam, (float)(ex * ex + ey * ey + ez * ez));
-            q = snap_b[s];
-            ex = p.x - q.x; ey = p.y - q.y; ez = p.z - q.z;
-            disp_image(ex, ey, ez, G);
-            dbm = fmaxf(dbm, (float)(ex * ex + ey * ey + ez * ez));
-        }
-    }
-    if (trk_part) {
-        __shared__ float sht[3][16];
-        dam = wave_max(dam); dbm = wave_max(dbm); v2m = wave_max(v2m);
-        if ((threadIdx.x & 63) == 0) { sht[0][threadIdx.x >> 6] = dam; sht[1][threadIdx.x >> 6] = dbm; sht[2][threadIdx.x >> 6] = v2m; }
-        __syncthreads();
-        if (threadIdx.x < 3) { float m = 0.f; for (int q = 0; q < (int)(blockDim.x >> 6); ++q) m = fmaxf(m, sht[threadIdx.x][q]); trk_part[threadIdx.x * gridDim.x + blockIdx.x] = m; }
-    }
-    if constexpr (CM) {
-        __shared__ double shm[4][4];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { px += __shfl_xor(px, o, 64); py += __shfl_xor(py, o, 64); pz += __shfl_xor(pz, o, 64); m += __shfl_xor(m, o, 64); }
-        const int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) { shm[w][0] = px; shm[w][1] = py; shm[w][2] = pz; shm[w][3] = m; }
-        __syncthreads();
-        if (threadIdx.x < 4) { double a = 0; for (int q = 0; q < (int)(blockDim.x >> 6); ++q) a += shm[q][threadIdx.x]; cm_out[4 * (int64_t)blockIdx.x + threadIdx.x] = a; }
-    }
-    if constexpr (TH) thermo_write_partial(mv2, thermo_noise_share<T>(th), th_out);
-}
-template <class T, bool CM, bool LAST>
-__global__ void k_vv_mid(int64_t n, typename Vec<T>::T4* pos, typename Vec<T>::T4* vel, const typename Vec<T>::T4* __restrict__ fr, T dt, T dt2,
-                         const double* __restrict__ cm_in, int n_cm_in, double* cm_out,
-                         const typename Vec<T>::T4* __restrict__ fa, GridP<T> G,
-                         const typename Vec<T>::T4* __restrict__ snap_a = nullptr, const typename Vec<T>::T4* __restrict__ snap_b = nullptr, float* trk_part = nullptr) {
-    vv_mid_body<T, CM, LAST, false>(n, pos, vel, fr, dt, dt2, cm_in, n_cm_in, cm_out, fa, G, snap_a, snap_b, trk_part, ThermoP{}, nullptr);
-}
-// the close launch of a coupled step: k_vv_mid<…, LAST> with the thermostat partials as one more output
-template <class T, bool CM>
-__global__ void k_vv_close(int64_t n, typename Vec<T>::T4* pos, typename Vec<T>::T4* vel, const typename Vec<T>::T4* __restrict__ fr, T dt, T dt2,
-                           const double* __restrict__ cm_in, int n_cm_in, double* cm_out,
-                           const typename Vec<T>::T4* __restrict__ fa, GridP<T> G, ThermoP th, double* th_out) {
-    vv_mid_body<T, CM, true, true>(n, pos, vel, fr, dt, dt2, cm_in, n_cm_in, cm_out, fa, G, nullptr, nullptr, nullptr, th, th_out);
-}
-
-// the scale, then the first kick + drift + wrap of the next step (k_vv1's arithmetic) and the maxima of the pair lists' validity check
-// as k_vv_mid measures them.  No position shift: the drift happens after the removal.
-template <class T>
-__global__ void __launch_bounds__(256) k_vv_open(int64_t n, typename Vec<T>::T4* pos, typename Vec<T>::T4* vel, const typename Vec<T>::T4* __restrict__ frc, T dt, T dt2,
-                                                 const double* __restrict__ cm_part, const double* __restrict__ th_part, int n_part, ThermoP P, GridP<T> G,
-                                                 const typename Vec<T>::T4* __restrict__ snap_a, const typename Vec<T>::T4* __restrict__ snap_b, float* trk_part) {
-    T vc[3];
-    const T lam = thermo_block_lambda<T>(cm_part, th_part, n_part, P, vc);
-    const bool sub = cm_part != nullptr;
-    float v2m = 0.f, dam = 0.f, dbm = 0.f;
-    for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
-        auto v = vel[s]; auto p = pos[s]; const auto f = frc[s];
-        thermo_scale<T>(v, vc, sub, lam);
-        v.x = step_add(v.x, accel_of(f.x, v.w), dt2); v.y = step_add(v.y, accel_of(f.y, v.w), dt2); v.z = step_add(v.z, accel_of(f.z, v.w), dt2);   // :594
-        p.x = step_add(p.x, v.x, dt); p.y = step_add(p.y, v.y, dt); p.z = step_add(p.z, v.z, dt);   // :602
-        wrap_point(p.x, p.y, p.z, G);                                          // :609
-        vel[s] = v; pos[s] = p;
-        if (trk_part) {
-            v2m = fmaxf(v2m, (float)(v.x * v.x + v.y * v.y + v.z * v.z));
-            auto q = snap_a[s];
-            T ex = p.x - q.x, ey = p.y - q.y, ez = p.z - q.z;
-            disp_image(ex, ey, ez, G);
-            dam = fmaxf(dam, (float)(ex * ex + ey * ey + ez * ez));
-            q = snap_b[s];
-            ex = p.x - q.x; ey = p.y - q.y; ez = p.z - q.z;
-            disp_image(ex, ey, ez, G);
-            dbm = fmaxf(dbm, (float)(ex * ex + ey * ey + ez * ez));
-        }
-    }
-    if (trk_part) {
-        __shared__ float sht[3][16];
-        dam = wave_max(dam); dbm = wave_max(dbm); v2m = wave_max(v2m);
-        if ((threadIdx.x & 63) == 0) { sht[0][threadIdx.x >> 6] = dam; sht[1][threadIdx.x >> 6] = dbm; sht[2][threadIdx.x >> 6] = v2m; }
-        __syncthreads();
-        if (threadIdx.x < 3) { float m = 0.f; for (int q = 0; q < (int)(blockDim.x >> 6); ++q) m = fmaxf(m, sht[threadIdx.x][q]); trk_part[threadIdx.x * gridDim.x + blockIdx.x] = m; }
-    }
-}
-
-// frc += fa: the same fold outside the integrator
-template <class T>
-__global__ void k_add_forces(int64_t n, typename Vec<T>::T4* frc, const typename Vec<T>::T4* __restrict__ fa) {
-    for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
-        auto f = frc[s];
-        if (fa) { const auto g = fa[s]; f.x += g.x; f.y += g.y; f.z += g.z; }
-        frc[s] = f;
-    }
-}
-
-// Σ m v and Σ m of the current velocities (for an explicit remove_CM_motion! / multi-GPU all-reduce)
-template <class T>
-__global__ void k_cm_partials(int64_t n, const typename Vec<T>::T4* __restrict__ vel, const T* __restrict__ vcm, double* cm_part) {
-    int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    double px = 0, py = 0, pz = 0, m = 0;
-    if (s < n) { auto v = vel[s]; if (vcm) { v.x -= vcm[0]; v.y -= vcm[1]; v.z -= vcm[2]; } px = (double)v.x * v.w; py = (double)v.y * v.w; pz = (double)v.z * v.w; m = v.w; }
-    __shared__ double sh[4][4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { px += __shfl_xor(px, o, 64); py += __shfl_xor(py, o, 64); pz += __shfl_xor(pz, o, 64); m += __shfl_xor(m, o, 64); }
-    int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh[w][0] = px; sh[w][1] = py; sh[w][2] = pz; sh[w][3] = m; }
-    __syncthreads();
-    if (threadIdx.x < 4) { double a = 0; for (int q = 0; q < (int)(blockDim.x >> 6); ++q) a += sh[q][threadIdx.x]; cm_part[4 * (int64_t)blockIdx.x + threadIdx.x] = a; }
-}
-
-// one block of 256 threads: fixed-order sum of the per-block partials → out4 = {Px,Py,Pz,M} (double), vcm = P/M (T)
-template <class T>
-__global__ void k_cm_finalize(int n_part, const double* __restrict__ cm_part, double* out4, T* vcm) {
-    __shared__ double sh[4][4];
-    double a[4] = {0, 0, 0, 0};
-    for (int q = threadIdx.x; q < n_part; q += blockDim.x) { const double* p = cm_part + 4 * (int64_t)q; a[0] += p[0]; a[1] += p[1]; a[2] += p[2]; a[3] += p[3]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) for (int c = 0; c < 4; ++c) a[c] += __shfl_xor(a[c], o, 64);
-    if ((threadIdx.x & 63) == 0) for (int c = 0; c < 4; ++c) sh[threadIdx.x >> 6][c] = a[c];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t[4] = {0, 0, 0, 0};
-        for (int q = 0; q < (int)(blockDim.x >> 6); ++q) for (int c = 0; c < 4; ++c) t[c] += sh[q][c];
-        for (int c = 0; c < 4; ++c) out4[c] = t[c];
-        if (vcm) for (int c = 0; c < 3; ++c) vcm[c] = (T)(t[c] / t[3]);
-    }
-}
-
-// vcm = P/M from a device-resident {Px,Py,Pz,M} (the all-reduced total of a multi-GPU run)
-template <class T>
-__global__ void k_vcm_from_total(const double* __restrict__ total4, T* vcm) {
-    if (threadIdx.x < 3) vcm[threadIdx.x] = (T)(total4[threadIdx.x] / total4[3]);
-}
-
-template <class T>
-__global__ void k_shift_vel(int64_t n, typename Vec<T>::T4* vel, const T* __restrict__ vcm, const double* __restrict__ cm_part, int n_cm_part,
-                            const int32_t* __restrict__ orig, const uint8_t* __restrict__ skip) {      // skip (nullable): per caller index, atoms left alone (virtual sites)
-    T vc[3];
-    if (cm_part) block_vcm<T>(cm_part, n_cm_part, vc);
-    else { vc[0] = vcm[0]; vc[1] = vcm[1]; vc[2] = vcm[2]; }
-    for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
-        if (orig && skip[orig[s]]) continue;
-        auto v = vel[s]; v.x -= vc[0]; v.y -= vc[1]; v.z -= vc[2]; vel[s] = v;
-    }
-}
-
-// the flush of a scale that the run's last step left pending (k_shift_vel's sibling); skip as there: a virtual site's velocity is left alone
-template <class T>
-__global__ void __launch_bounds__(256) k_scale_vel(int64_t n, typename Vec<T>::T4* vel, const double* __restrict__ cm_part, const double* __restrict__ th_part, int n_part, ThermoP P,
-                                                   const int32_t* __restrict__ orig, const uint8_t* __restrict__ skip) {
-    T vc[3];
-    const T lam = thermo_block_lambda<T>(cm_part, th_part, n_part, P, vc);
-    const bool sub = cm_part != nullptr;
-    for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
-        if (orig && skip[orig[s]]) continue;
-        auto v = vel[s];
-        thermo_scale<T>(v, vc, sub, lam);
-        vel[s] = v;
-    }
-}
-
-// kinetic energy partials: Σ (m/2) v·v  (energy.jl:56-89)
-template <class T>
-__global__ void k_ke_partials(int64_t n, const typename Vec<T>::T4* __restrict__ vel, double* part) {
-    int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    double k = 0;
-    if (s < n) { auto v = vel[s]; k = 0.5 * (double)v.w * ((double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z); }
-    __shared__ double sh[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) k += __shfl_xor(k, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = k;
-    __syncthreads();
-    if (threadIdx.x == 0) { double a = 0; for (int q = 0; q < (int)(blockDim.x >> 6); ++q) a += sh[q]; part[blockIdx.x] = a; }
-}
-
-// fixed-order sum of n doubles per block: block c sums part[c·n .. (c+1)·n) into out[c] (component-major partial arrays)
-[[maybe_unused]] static __global__ void k_sum_double(int n, const double* __restrict__ part, double* out) {
-    __shared__ double sh[256];
-    part += (size_t)blockIdx.x * n;
-    double a = 0;
-    for (int q = threadIdx.x; q < n; q += blockDim.x) a += part[q];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) { double t = 0; for (int q = 0; q < (int)blockDim.x; ++q) t += sh[q]; out[blockIdx.x] = t; }
-}
-
-template <class T>
-__global__ void k_check_finite(int64_t n, const typename Vec<T>::T4* __restrict__ pos, const typename Vec<T>::T4* __restrict__ vel,
-                               const typename Vec<T>::T4* __restrict__ frc, int32_t* flags) {
-    int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (s >= n) return;
-    auto p = pos[s]; auto v = vel[s]; auto f = frc[s];
-    T t = p.x + p.y + p.z + v.x + v.y + v.z + f.x + f.y + f.z;
-    if (!(t == t) || M<T>::fabs(t) > T(1e30)) atomicOr(&flags[FLAG_NAN], 1);
-}
-
-// ---------------------------------------------------------------------------------------------------
 // multi-GPU halo helpers
 template <class T>
 __global__ void k_gather_coords(int64_t n, const int32_t* __restrict__ idx, const T* __restrict__ shift, const int32_t* __restrict__ inv,
@@ -2445,10 +2139,8 @@ __global__ void __launch_bounds__(256) k_halo_pack(int64_t n, const int32_t* __r
     if (blockIdx.x == gridDim.x - 1) {
         __shared__ double tot[4];
         __shared__ double sh_cm[4][4];
-        double a[4] = {0, 0, 0, 0};
-        if (cm_part) for (int q = threadIdx.x; q < n_part; q += blockDim.x) { const double* p = cm_part + 4 * (int64_t)q; a[0] += p[0]; a[1] += p[1]; a[2] += p[2]; a[3] += p[3]; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) for (int c = 0; c < 4; ++c) a[c] += __shfl_xor(a[c], o, 64);
+        double a[4];
+        cm_partials_wave_sum(cm_part, cm_part ? n_part : 0, a);
         if ((threadIdx.x & 63) == 0) for (int c = 0; c < 4; ++c) sh_cm[threadIdx.x >> 6][c] = a[c];
         __syncthreads();
         if (threadIdx.x < 4) { double t = 0; for (int q = 0; q < (int)(blockDim.x >> 6); ++q) t += sh_cm[q][threadIdx.x]; tot[threadIdx.x] = t; if (cm_own) cm_own[threadIdx.x] = t; }

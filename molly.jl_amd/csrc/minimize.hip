@@ -177,20 +177,8 @@ __global__ void __launch_bounds__(MIN_BLOCK) k_min_settle(int64_t n, typename Ve
     for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
         auto p = pos[s];
         if (back) { const auto q = keep[orig[s]]; p.x = q.x; p.y = q.y; p.z = q.z; pos[s] = p; }
-        if (snap_in) {
-            const auto q = snap_in[s];
-            T ex = p.x - q.x, ey = p.y - q.y, ez = p.z - q.z;
-            disp_image(ex, ey, ez, G);
-            const float d2 = (float)(ex * ex + ey * ey + ez * ez);
-            da = (d2 > da || d2 != d2) ? d2 : da;
-        }
-        if (snap_out) {
-            const auto q = snap_out[s];
-            T ex = p.x - q.x, ey = p.y - q.y, ez = p.z - q.z;
-            disp_image(ex, ey, ez, G);
-            const float d2 = (float)(ex * ex + ey * ey + ez * ez);
-            db = (d2 > db || d2 != d2) ? d2 : db;
-        }
+        if (snap_in) da = nan_max(da, disp2_from(p.x, p.y, p.z, snap_in[s], G));
+        if (snap_out) db = nan_max(db, disp2_from(p.x, p.y, p.z, snap_out[s], G));
     }
     da = block_nan_max(da);
     db = block_nan_max(db);

@@ -1,7 +1,7 @@
 // stochastic.hip — Philox4x32-10 noise, the fused Langevin update, Andersen / Maxwell-Boltzmann velocity draws (see stochastic.h)
 #include "stochastic.h"
 
-#include "kernels.h"
+#include "integrate.h"
 #include "philox.h"
 
 namespace mhip {
@@ -16,28 +16,18 @@ __global__ void __launch_bounds__(256) k_langevin(int64_t n, typename Vec<T>::T4
                                                   const int32_t* __restrict__ orig, StochP<T> P, const T* __restrict__ vcm, const double* __restrict__ cm_in,
                                                   int n_cm_in, double* cm_out, GridP<T> G, const typename Vec<T>::T4* __restrict__ frc_add) {
 #pragma clang fp contract(off)
-    T vc[3] = {T(0), T(0), T(0)};
-    const bool sub = vcm != nullptr || cm_in != nullptr;
-    if (cm_in) block_vcm<T>(cm_in, n_cm_in, vc);
-    else if (vcm) { vc[0] = vcm[0]; vc[1] = vcm[1]; vc[2] = vcm[2]; }
+    T vc[3];
+    const bool sub = pending_vcm<T>(vcm, cm_in, n_cm_in, vc);
     double px = 0, py = 0, pz = 0, m = 0;
     for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
         auto v = vel[s]; auto p = pos[s]; auto f = frc[s];
         if (frc_add) { const auto g = frc_add[s]; f.x += g.x; f.y += g.y; f.z += g.z; }      // (the side array of a small system's step: bonded sums — what k_add_forces folded in a launch of its own)
-        if (sub) { v.x -= vc[0]; v.y -= vc[1]; v.z -= vc[2]; }
+        if (sub) cm_remove(v, vc);
         langevin_atom<T>(v, p, f, P, (uint64_t)orig[s] + 1, G);
         vel[s] = v; pos[s] = p;
         if constexpr (CM) { px += (double)v.x * v.w; py += (double)v.y * v.w; pz += (double)v.z * v.w; m += v.w; }
     }
-    if constexpr (CM) {
-        __shared__ double sh[4][4];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { px += __shfl_xor(px, o, 64); py += __shfl_xor(py, o, 64); pz += __shfl_xor(pz, o, 64); m += __shfl_xor(m, o, 64); }
-        const int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) { sh[w][0] = px; sh[w][1] = py; sh[w][2] = pz; sh[w][3] = m; }
-        __syncthreads();
-        if (threadIdx.x < 4) { double a = 0; for (int q = 0; q < (int)(blockDim.x >> 6); ++q) a += sh[q][threadIdx.x]; cm_out[4 * (int64_t)blockIdx.x + threadIdx.x] = a; }
-    }
+    if constexpr (CM) block_cm_write(px, py, pz, m, cm_out);
 }
 
 // MODE 0 (Andersen): the first two Philox words of block ctr0 decide, the velocity comes from block ctr0 + natoms (kernels.jl:714-720);
@@ -45,17 +35,15 @@ __global__ void __launch_bounds__(256) k_langevin(int64_t n, typename Vec<T>::T4
 template <class T, int MODE>
 __global__ void __launch_bounds__(256) k_redraw(int64_t n, typename Vec<T>::T4* vel, const int32_t* __restrict__ orig, StochP<T> P,
                                                 const T* __restrict__ vcm, const double* __restrict__ cm_in, int n_cm_in, const uint8_t* __restrict__ site) {
-    T vc[3] = {T(0), T(0), T(0)};
-    const bool sub = vcm != nullptr || cm_in != nullptr;
-    if (cm_in) block_vcm<T>(cm_in, n_cm_in, vc);
-    else if (vcm) { vc[0] = vcm[0]; vc[1] = vcm[1]; vc[2] = vcm[2]; }
+    T vc[3];
+    const bool sub = pending_vcm<T>(vcm, cm_in, n_cm_in, vc);
     for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
         auto v = vel[s];
         if (site && site[orig[s]]) {      // a virtual site (per caller index): random_velocities! zeroes it (spatial.jl:823-831), the thermostat and the CM removal leave it alone (coupling.jl:209)
             if constexpr (MODE == 1) { v.x = v.y = v.z = T(0); vel[s] = v; }
             continue;
         }
-        if (sub) { v.x -= vc[0]; v.y -= vc[1]; v.z -= vc[2]; }
+        if (sub) cm_remove(v, vc);
         uint64_t ctr0 = (uint64_t)orig[s] + 1;
         bool draw = true;
         if constexpr (MODE == 0) {

@@ -5,7 +5,7 @@
 //   open   every block re-sums both partial arrays in the same fixed order (thermo_block_lambda), calls thermostat_lambda, scales
 //          v = λ·(v − v_cm) and carries on with the first kick, the drift and the wrap (k_vv_open, k_con_thermo<…, 0>).
 // The run's last step has no open: k_scale_vel applies the same λ·(v − v_cm) in the same operation order.  (The helpers are here, the
-// kernels with the integrators they belong to: kernels.h, constraints.hip.)
+// kernels with the integrators they belong to: integrate.h, constraints.hip.)
 // CSVR noise: atom i (caller index) owns the three normals randn3(i + 1, ctr1 + step, key) — the ones mhip_random_velocities would draw
 // for it; numbered k = 3i + c, R is k = 0 and S = Σ ξ_k² over 1 <= k <= dof − 1.  The close launch's lanes stride over the CALLER
 // indices, so the sum depends neither on the sorted order of the moment nor on how a run is cut into calls.
@@ -33,7 +33,7 @@ template <class T> __device__ inline double thermo_noise_share(const ThermoP& P)
     }
     return xi2;
 }
-// th_out[2·block + {0, 1}] = the block's {Σ m|v|², Σ ξ²}: waves by shuffle, then the waves in order (the order k_vv_mid uses for Σ m v)
+// th_out[2·block + {0, 1}] = the block's {Σ m|v|², Σ ξ²}: waves by shuffle, then the waves in order (block_cm_write's order, integrate.h)
 __device__ inline void thermo_write_partial(double mv2, double xi2, double* th_out) {
     __shared__ double sh_th[16][2];
 #pragma unroll
@@ -44,8 +44,10 @@ __device__ inline void thermo_write_partial(double mv2, double xi2, double* th_o
 }
 
 // ---- open ----------------------------------------------------------------------------------------------------------------------------
-// Every block: the n_part partials of the close launch re-summed in block_vcm's order (cm_part null: the step removes no CM motion),
+// Every block: the n_part partials of the close launch re-summed in block_cm_total's order (cm_part null: the step removes no CM motion),
 // v_cm = P / M rounded to T as block_vcm does, λ in double rounded to T once.  Block 0 keeps the info record.
+// (Six values wide, one barrier: sharing block_cm_total's four would mean a second re-sum for the thermostat's two, with its own barrier, or a branch
+// on the caller inside the shared one — it stays a sum of its own, in the same order.  blockDim.x <= 1024.)
 template <class T>
 __device__ inline T thermo_block_lambda(const double* __restrict__ cm_part, const double* __restrict__ th_part, int n_part, const ThermoP& P, T* vcm3) {
     __shared__ double sh_tl[16][6];
