@@ -24,6 +24,7 @@
 #include "kernels.h"
 #include "integrate.h"
 #include "list_policy.h"
+#include "step_plan.h"
 #include "held.h"
 #include "admit.h"
 #include "replan.h"
@@ -305,7 +306,7 @@ template <class T> class Engine final : public EngineBase {
         setup_inter(); setup_grid();
         for (int k = 0; k < 2; ++k) { pos[k].reserve(cap); vel[k].reserve(cap); frc[k].reserve(cap); lj[k].reserve(cap); orig[k].reserve(cap); }
         inv.reserve(cap); key_in.reserve(cap); key_out.reserve(cap); idx_in.reserve(cap); perm.reserve(cap);
-        flags.reserve(N_FLAGS); red_out.reserve(8); vcm.reserve(4); cm_step.reserve(2 * 4 * 1024);   // two halves: k_vv_mid reads one while it writes the other
+        flags.reserve(N_FLAGS); red_out.reserve(8); vcm.reserve(4); cm_step.reserve(2 * 4 * CM_HALF_PARTS);   // two halves: k_vv_mid reads one while it writes the other
         h_flags.make(N_FLAGS); h_red.make(8);
         for (int k = 0; k < 2; ++k) { MHIP_HIP(hipMemsetAsync(pos[k].p, 0, cap * sizeof(T4), stream)); MHIP_HIP(hipMemsetAsync(vel[k].p, 0, cap * sizeof(T4), stream)); MHIP_HIP(hipMemsetAsync(frc[k].p, 0, cap * sizeof(T4), stream)); MHIP_HIP(hipMemsetAsync(lj[k].p, 0, cap * sizeof(T2), stream)); }
         std::vector<int32_t> iota(cap); for (int64_t i = 0; i < cap; ++i) iota[i] = (int32_t)i;
@@ -545,7 +546,7 @@ template <class T> class Engine final : public EngineBase {
 
     void flush_cm() {
         if (!pending_cm.mode()) return;
-        hipLaunchKernelGGL(k_shift_vel<T>, dim3(std::min(cdiv(n_owned, 256), 1024)), dim3(256), 0, stream, n_owned, vel[cur].p, (const T*)vcm.p,
+        hipLaunchKernelGGL(k_shift_vel<T>, dim3(stage_blocks(n_owned)), dim3(256), 0, stream, n_owned, vel[cur].p, (const T*)vcm.p,
                            pending_cm.parts_arg(), pending_cm.n, vs_on ? (const int32_t*)orig[cur].p : nullptr, (const uint8_t*)vs_flag.p);      // (spatial.jl:926: a site's velocity is left alone)
         pending_cm.none();
     }
@@ -749,10 +750,9 @@ template <class T> class Engine final : public EngineBase {
     // 14 % through a different register assignment, with the same instructions: measured, dropped.)
     DBuf<float> trk_part, trk_out; Pinned<float> h_trk; Event ev_trk;
     int64_t trk_step = -1, trk_prune_id = -1, trk_outer_id = -1; double trk_prev_vmax = 0;   // (ids: the running counts of prunes / outer searches)
-    bool in_vv_fused = false;      // inside the fused step loop of vv_loop (async_ok and the pair pass's Σ m v summing read it)
-    bool in_lang_fused = false;      // inside mhip_langevin_run of a small system whose last force launch integrates (the pair launch's extra workgroup then sums the Σ m v partials, as inside mhip_vv_run)
-    bool in_lang_async = false;      // … and whose list checks are measured by that launch (no Andersen coupling behind it: the speeds the check reads would not be the run's)
-    bool async_ok() const { return (in_vv_fused || in_lang_async) && dual && n_ghost == 0 && !host_prune && held.inner_list_stands(); }
+    RunPlan run;      // the step loop the context is inside of (step_plan.h); outside one: the two-launch step of the stage entry points
+    struct InLoop { RunPlan& r; InLoop(RunPlan& m, const RunPlan& p) : r(m) { r = p; } ~InLoop() { r = RunPlan{}; } };
+    bool async_ok() const { return run.async && dual && n_ghost == 0 && !host_prune && held.inner_list_stands(); }
     // room for the per-block maxima of a check measured by n_parts blocks
     void trk_reserve(int n_parts) { trk_part.reserve(3 * (size_t)std::max(n_parts, 1024)); trk_out.reserve(4); }
     // the check of `step` from the n_parts per-block maxima in trk_part: reduce, copy, event
@@ -900,7 +900,7 @@ template <class T> class Engine final : public EngineBase {
         s.gs = gs_groups(); s.gs_list_current = gs_list_id == n_filters; s.n_ghost = n_ghost;
         s.energy = energy; s.part = part; s.allow_gs = allow_gs; s.own_frc = req.frc != nullptr;
         s.step = req.step; s.halo = req.halo; s.fuse_step = fuse_step_env;
-        s.cm_mode = pending_cm.mode(); s.cm_n = pending_cm.n; s.in_step_loop = in_vv_fused || in_lang_fused;
+        s.cm_mode = pending_cm.mode(); s.cm_n = pending_cm.n; s.in_step_loop = run.pass_sums_cm;
         return s;
     }
     static void throw_capacity(const PassPlan& plan) { if (plan.capacity != PassCapacity::OK) throw ApiError{MHIP_ERR_CAPACITY, capacity_message(plan.capacity)}; }
@@ -1195,8 +1195,8 @@ template <class T> class Engine final : public EngineBase {
     void halo_fused(int64_t step_n, double dt, bool cm, bool measure) {
         lp.cur_dt = dt;
         if (lp.check_due(step_n, rebuild_every()) && step_n != last_build_step && dual) refresh(step_n);
-        PassReq req;
-        req.step = true; req.cm = cm; req.measure = measure; req.dt = dt; req.halo = true; req.halo_cm_in = halo_cm_in;
+        PassReq req = pass_req(fused_halo_request(cm, measure), dt);
+        req.halo = true; req.halo_cm_in = halo_cm_in;
         const PassRes res = step_forces(step_n, req);
         if (!res.step) throw ApiError{MHIP_ERR_STATE, "internal: the fused ghosted step did not launch"};
         step_parts = res.parts;
@@ -1352,7 +1352,7 @@ template <class T> class Engine final : public EngineBase {
     // frc[cur] += the second force array, for consumers other than the second kick
     void fold_side_forces() {
         if (!pend_a) return;
-        hipLaunchKernelGGL(k_add_forces<T>, dim3(std::min(cdiv(n_owned, 256), 1024)), dim3(256), 0, stream, n_owned, frc[cur].p, pend_a);
+        hipLaunchKernelGGL(k_add_forces<T>, dim3(stage_blocks(n_owned)), dim3(256), 0, stream, n_owned, frc[cur].p, pend_a);
         pend_a = nullptr;
     }
 
@@ -1778,26 +1778,16 @@ template <class T> class Engine final : public EngineBase {
     void vv_stage1(double dt) override { admit(adm::VV_STAGE1); stage1_impl(dt); }
     void stage1_impl(double dt) {      // first kick + drift: the forces of the coordinates held are in place
         lp.cur_dt = dt;
-        tr("k_vv1");
-        prof.begin(2, stream);
-        hipLaunchKernelGGL(k_vv1<T>, dim3(std::min(cdiv(n_owned, 256), 1024)), dim3(256), 0, stream, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, T(dt), T(dt) / T(2),
-                           pending_cm.vcm_arg(vcm.p), pending_cm.parts_arg(), pending_cm.n, G);
-        prof.end(2, stream);
+        launch_stage(plan_open(run, step_shape(0, false, 0)), 0, dt, nullptr);
         pending_cm.none();
     }
+    // the closing kick of the two-launch form (k_vv2); with a partial buffer of the caller's every one of its n_parts_ext slots gets a block (blocks without atoms write zeros)
     void stage2_impl(int64_t step_n, double dt, bool cm, double* cm_parts_ext = nullptr, int n_parts_ext = 0) {
         step_forces(step_n);
-        // with an external partial buffer every one of its n_parts_ext slots gets a block (blocks without atoms write zeros)
-        const int nb = cm_parts_ext ? n_parts_ext : std::min(cdiv(n_owned, 256), 1024);
-        tr("k_vv2");
-        prof.begin(2, stream);
-        if (cm) {
-            hipLaunchKernelGGL((k_vv2<T, true>), dim3(nb), dim3(256), 0, stream, n_owned, vel[cur].p, frc[cur].p, T(dt) / T(2), cm_parts_ext ? cm_parts_ext : cm_step.p, pend_a);
-            pending_cm.resum(cm_step.p, nb);   // the next k_vv1 (or any flush) re-sums the partials: no finalize launch (those in cm_parts_ext: halo_end_parts drops this at once)
-        } else {
-            hipLaunchKernelGGL((k_vv2<T, false>), dim3(nb), dim3(256), 0, stream, n_owned, vel[cur].p, frc[cur].p, T(dt) / T(2), (double*)nullptr, pend_a);
-        }
-        prof.end(2, stream);
+        const StepShape s = step_shape(step_n, true, cm ? 1 : 0, cm_parts_ext ? n_parts_ext : 0);
+        const StagePlan p = plan_stage(run, s, plan_request(run, s), false);
+        launch_stage(p, step_n, dt, cm_out_of(p, 0, cm_parts_ext));
+        if (p.repend) pending_cm.resum(cm_step.p, p.nb);   // the next k_vv1 (or any flush) re-sums the partials: no finalize launch
         pend_a = nullptr;    // the kick wrote the total back into frc[cur]
     }
     // the neighbour cadence of a stepwise-driven run: as in vv_run.  A ghosted sub-domain without the dual list is re-planned
@@ -1822,7 +1812,7 @@ template <class T> class Engine final : public EngineBase {
         if (cm_parts_dev && (n_parts < 1 || n_parts > 1024)) throw ApiError{MHIP_ERR_INVALID, "n_parts must be 1..1024"};
         scatter_coords(first, n, in_dev);
         stage2_cadenced(step_n, dt, cm_parts_dev != nullptr, cm_parts_dev, n_parts);
-        if (cm_parts_dev) pending_cm.none();
+        if (cm_parts_dev) { pending_cm.none(); pending_cm.n = n_parts; }
         MHIP_HIP(hipGetLastError());
     }
     void remove_cm_parts_dev(const double* total_parts_dev, int32_t n_parts) override {
@@ -1960,23 +1950,23 @@ template <class T> class Engine final : public EngineBase {
         // … which workgroup 0 of the pair pass in between adds up into ONE partial, as inside mhip_vv_run (ForceArgs::cm_fin_in): the integrator's blocks
         // then do not each re-sum hundreds of partials first
         PassReq req;
-        req.cm_sum_in = (solo && halo_cm_in && n_ghost == 0 && pending_cm.n > 1 && pending_cm.n <= 4096) ? (const double*)cm_step.p + (size_t)(cm_half ^ 1) * 4 * 1024 : (const double*)nullptr;
+        req.cm_sum_in = (solo && halo_cm_in && n_ghost == 0 && pending_cm.n > 1 && pending_cm.n <= 4096) ? (const double*)cm_step_half(cm_half ^ 1) : (const double*)nullptr;
         const bool summed = step_forces(step_n, req).cm_summed;
         flush_cm();                                                               // (a removal registered through the stepwise entry points)
-        const double* cm_in = halo_cm_in ? (solo ? (summed ? (const double*)cm_fin_buf.p : (const double*)cm_step.p + (size_t)(cm_half ^ 1) * 4 * 1024) : (const double*)cm_all.p) : (const double*)nullptr;
+        const double* cm_in = halo_cm_in ? (solo ? (summed ? (const double*)cm_fin_buf.p : (const double*)cm_step_half(cm_half ^ 1)) : (const double*)cm_all.p) : (const double*)nullptr;
         const int n_in = solo ? (summed ? 1 : pending_cm.n) : 1 + hp.n_cm_peers;
-        // (block count: mhip_vv_run's — fewer, longer blocks at these sizes, see there)
-        const int nb = (cm && last) ? n_parts : std::min(cdiv(n_owned, 256), solo ? (int)std::max<int64_t>(256, std::min<int64_t>(512, n_owned / 2048)) : 1024);
-        double* cm_out = cm ? (last ? cm_parts_dev : cm_step.p + (size_t)(solo ? cm_half : 0) * 4 * 1024) : (double*)nullptr;
-        prof.begin(2, stream);
-        tr("k_vv_mid");
-        vv_mid_launch(cm, last, nb, dt, cm_in, n_in, cm_out, false);
-        prof.end(2, stream);
+        // (planned behind the pass: it may have given the dual list up; the cadence decision is the one taken in front of it)
+        StepShape s = step_shape(step_n, last, cm ? 1 : 0, n_parts);
+        s.due = due; s.solo = solo;
+        const RunPlan stepwise = plan_run(run_shape(Loop::STEPWISE));
+        const StagePlan p = plan_stage(stepwise, s, plan_request(stepwise, s), false);
+        launch_stage(p, step_n, dt, cm_out_of(p, cm_half, cm_parts_dev), nullptr, cm_in, n_in);
         step_closed(!last);
-        if (due && !dual) refresh(step_n);
+        if (p.refresh_behind) refresh(step_n);
+        if (p.flip) cm_half ^= 1;
         if (!last) {
-            pending_cm.n = nb;
-            if (solo) cm_half ^= 1; else halo_pack(cm);
+            pending_cm.n = p.nb;
+            if (!solo) halo_pack(cm);
             halo_cm_in = cm;
         } else halo_cm_in = false;
         MHIP_HIP(hipGetLastError());
@@ -2450,15 +2440,59 @@ template <class T> class Engine final : public EngineBase {
         drifted();
         if (cm) { pending_cm.resum(cm_blk.p + (size_t)step_half * 4 * res.parts, res.parts); step_half ^= 1; }
     }
-    // one k_vv_mid launch of nb blocks (last: the closing kick alone); measure: the maxima of the next step's check into trk_part
-    void vv_mid_launch(bool cm, bool last, int nb, double dt, const double* cm_in, int n_in, double* cm_out, bool measure) {
-        auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, stream, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, T(dt), T(dt) / T(2),
-                               cm_in, n_in, cm_out, (const T4*)pend_a, G,
-                               measure ? (const T4*)pos_snap_in.p : (const T4*)nullptr, measure ? (const T4*)pos_snap.p : (const T4*)nullptr, measure ? trk_part.p : (float*)nullptr);
-        };
-        if (last) { if (cm) go(k_vv_mid<T, true, true>); else go(k_vv_mid<T, false, true>); }
-        else { if (cm) go(k_vv_mid<T, true, false>); else go(k_vv_mid<T, false, false>); }
+    // ---- the integrator stage: planned on the host (step_plan.h), launched here --------------------------------------------------------------
+    RunShape run_shape(Loop loop) const { return RunShape{loop, andersen_prob > 0, items_on(), bonded.any(), pme.on(), dual, fuse_step_env, fuse_gcv_env}; }
+    // the step as the planner sees it, read at the moment of the call; n_parts_last: the slots of a partial buffer of the caller's for this step's Σ m v, 0: none
+    StepShape step_shape(int64_t step, bool last, int remove_cm_every, int n_parts_last = 0) const {
+        StepShape s;
+        s.step = step; s.last = last; s.remove_cm_every = remove_cm_every; s.thermo_every = thermo_on() ? thermo.n_steps : 0;
+        s.due = lp.check_due(step, rebuild_every()); s.due_next = lp.check_due(step + 1, rebuild_every());
+        s.async_ok = async_ok(); s.trk_issued = held.trk_issued();
+        s.n_atoms = n_owned; s.item_blocks = items_on() ? con_blocks() : 1; s.n_parts_last = n_parts_last;
+        return s;
+    }
+    PassReq pass_req(const StepRequest& q, double dt, const StochP<T>* lang = nullptr) const { PassReq r; r.step = q.step; r.gcv = q.gcv; r.cm = q.cm; r.measure = q.measure; r.dt = dt; r.lang = lang; return r; }
+    double* cm_step_half(int half) const { return cm_step.p + (size_t)half * 4 * CM_HALF_PARTS; }
+    double* cm_out_of(const StagePlan& p, int half, double* caller) const {
+        return p.dest == CmDest::NONE ? nullptr : p.dest == CmDest::CALLER ? caller : cm_step_half(p.dest == CmDest::ENGINE_HALF ? half : 0);
+    }
+    // one launch form of the integrator stage.  cm_in / n_in: the Σ m v partials of the step before as k_vv_mid reads them (the other forms take the pending removal
+    // themselves); S: the Langevin parameters.  The check a launch measured is issued behind it; what the launch consumed is the caller's to book.
+    void launch_stage(const StagePlan& p, int64_t step, double dt, double* cm_out, const StochP<T>* S = nullptr) { launch_stage(p, step, dt, cm_out, S, pending_cm.parts_arg(), pending_cm.n); }
+    void launch_stage(const StagePlan& p, int64_t step, double dt, double* cm_out, const StochP<T>* S, const double* cm_in, int n_in) {
+        if (p.form == StageForm::NONE) return;
+        prof.begin(2, stream);
+        if (p.measure) trk_reserve(n_blocks);
+        const dim3 grid(p.nb), block(256);
+        switch (p.form) {
+        case StageForm::VV1:
+            tr("k_vv1");
+            hipLaunchKernelGGL(k_vv1<T>, grid, block, 0, stream, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, T(dt), T(dt) / T(2), pending_cm.vcm_arg(vcm.p), pending_cm.parts_arg(), pending_cm.n, G);
+            break;
+        case StageForm::VV2:
+            tr("k_vv2");
+            if (p.cm) hipLaunchKernelGGL((k_vv2<T, true>), grid, block, 0, stream, n_owned, vel[cur].p, frc[cur].p, T(dt) / T(2), cm_out, pend_a);
+            else hipLaunchKernelGGL((k_vv2<T, false>), grid, block, 0, stream, n_owned, vel[cur].p, frc[cur].p, T(dt) / T(2), (double*)nullptr, pend_a);
+            break;
+        case StageForm::VV_MID: {
+            tr("k_vv_mid");
+            auto go = [&](auto kern) {
+                hipLaunchKernelGGL(kern, grid, block, 0, stream, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, T(dt), T(dt) / T(2), cm_in, n_in, cm_out, (const T4*)pend_a, G,
+                                   p.measure ? (const T4*)pos_snap_in.p : (const T4*)nullptr, p.measure ? (const T4*)pos_snap.p : (const T4*)nullptr, p.measure ? trk_part.p : (float*)nullptr);
+            };
+            if (p.last) { if (p.cm) go(k_vv_mid<T, true, true>); else go(k_vv_mid<T, false, true>); }
+            else { if (p.cm) go(k_vv_mid<T, true, false>); else go(k_vv_mid<T, false, false>); }
+            break;
+        }
+        case StageForm::CON_STEP: con_launch(p.con_mode, p.nb, dt, cm_out, p.measure, S); break;
+        case StageForm::THERMO: case StageForm::THERMO_LAST: thermo_step(p, step, dt, cm_out); break;
+        case StageForm::LANGEVIN:      // (the side array of a small system's step is added by the update itself, as k_vv_mid does: no k_add_forces launch)
+            launch_langevin<T>(stream, p.nb, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, orig[cur].p, *S, pending_cm.vcm_arg(vcm.p), pending_cm.parts_arg(), pending_cm.n, cm_out, G, (const T4*)pend_a);
+            break;
+        default: break;
+        }
+        prof.end(2, stream);
+        if (p.measure) issue_track(p.nb, p.check_step);
     }
 
     void vv_run(int64_t first_step, int64_t n_steps, double dt, int remove_cm_every) override {
@@ -2485,68 +2519,45 @@ template <class T> class Engine final : public EngineBase {
     // No force launch integrates then (they update one atom per lane and cannot see a cluster's partners).
     void vv_loop(int64_t first_step, int64_t n_steps, double dt, int remove_cm_every, double* cm_parts_last, int n_parts_last) {
         const int every = rebuild_every();
-        // fused stepping: first kick + drift once, then ONE integrator launch between consecutive force passes (k_vv_mid), the
-        // plain second kick at the end.  The Andersen thermostat needs v_n between the kicks: the two-launch form then (never with constraints: set_andersen refuses them).
-        // A rescaling thermostat (thermostat.h) keeps the fused form; on the steps where it applies the integrator stage is a close and an open launch (thermo_step).
-        const bool fused = !(andersen_prob > 0);
-        InRun guard_fused(in_vv_fused); in_vv_fused = fused;
-        const bool pre = dual;                                                    // without the dual list: the reference's order
+        // fused stepping: first kick + drift once, then ONE integrator launch between consecutive force passes, the plain second kick at the end.  The Andersen
+        // thermostat needs v_n between the kicks: the two-launch form then (never with constraints: set_andersen refuses them).  A rescaling thermostat
+        // (thermostat.h) keeps the fused form; on the steps where it applies the integrator stage is a close and an open launch (thermo_step).
+        InLoop guard_loop(run, plan_run(run_shape(Loop::VV)));
         const int64_t last = first_step + n_steps;
+        const int n_parts_out = cm_parts_last ? n_parts_last : 0;
         int half = 0;
-        if (fused && n_steps > 0) {
-            if (items_on()) {
-                prof.begin(2, stream);
-                con_launch(0, con_blocks(), dt, nullptr, false, nullptr);
-                prof.end(2, stream);
-                drifted();
-            } else stage1_impl(dt);
-        }
+        const StagePlan open = plan_open(run, step_shape(first_step, false, 0), run.fused ? n_steps : 0);
+        launch_stage(open, first_step, dt, nullptr);
+        if (open.form != StageForm::NONE) { if (run.items) drifted(); else pending_cm.none(); }
         for (int64_t step = first_step + 1; step <= last; ++step) {
-            if (!fused) stage1_impl(dt);                                          // :594-609
+            if (!run.fused) stage1_impl(dt);                                      // :594-609
             // find_neighbors at step % n_steps == 0 (:645, neighbors.jl:396) builds the list from the coordinates of THIS step; it is
             // scheduled before the force pass so that, with the dual pair list, that pass can prune the outer list on the way.
             // Forces are unaffected: the pass walks a superset of the old list and every interaction has a cutoff <= r_list.
-            if (held.trk_issued() && step > trk_step) resolve_track(step);
-            if (pre && lp.check_due(step, every)) refresh(step);
-            const bool cm = remove_cm_every != 0 && step % remove_cm_every == 0;
-            const bool th = thermo_on() && step % thermo.n_steps == 0;            // :630, behind this step's CM removal
-            if (!fused) {
-                stage2_impl(step, dt, cm);                                        // :612-628
+            if (held.trk_issued() && resolve_due(run, step, trk_step)) resolve_track(step);
+            if (run.pre && lp.check_due(step, every)) refresh(step);
+            if (!run.fused) {
+                stage2_impl(step, dt, remove_cm_every != 0 && step % remove_cm_every == 0);      // :612-628
                 apply_coupling(step);                                             // :630
-                if (!pre && lp.check_due(step, every)) refresh(step);
+                if (!run.pre && lp.check_due(step, every)) refresh(step);
                 continue;
             }
             // the validity check of step + 1 is measured where its coordinates are made: by this step's integrator launch — or by the pair pass itself when it integrates
-            const bool measure = step != last && async_ok() && !held.trk_issued() && lp.check_due(step + 1, every);
-            const bool integrate = step != last && !items_on() && !th;            // (λ needs Σ m v² of ALL atoms between the kicks: no force launch integrates on such a step)
-            PassReq req;
-            req.step = integrate && !bonded.any() && !pme.on(); req.cm = cm;      // (one kernel either way: its stage time is its own, so the stage timers leave it fused)
-            req.gcv = integrate && bonded.any() && pme.on() && (pre || !lp.check_due(step, every));      // (a re-sort behind the pass would want the total force array)
-            req.measure = measure; req.dt = dt;
-            const PassRes res = step_forces(step, req);
+            const StepRequest q = plan_request(run, step_shape(step, step == last, remove_cm_every, n_parts_out));
+            const PassRes res = step_forces(step, pass_req(q, dt));      // (one kernel either way: its stage time is its own, so the stage timers leave it fused)
             if (res.step) {      // the pair pass integrated on the way (k_forces STEP): no integrator launch for this step
-                after_fused_step(res, measure, step + 1, cm);
+                after_fused_step(res, q.measure, step + 1, q.cm);
                 continue;
             }
-            if (!pre && lp.check_due(step, every)) { fold_side_forces(); refresh(step); }   // the sort permutes vel / frc with the atoms; Σ m v does not care
-            // every block re-sums the previous step's per-block Σ m v partials (32 bytes each), so fewer, longer blocks pay: 1024 blocks
-            // re-read 32 MB from L2 per launch — more than the 21 MB of atoms of the 256k-atom fluid (13.0 → 10.0 µs with 256 blocks;
-            // 1M atoms: 21.2 → 20.2 µs with 512, 21.8 with 256)
-            const bool parts_out = step == last && cm && cm_parts_last != nullptr;
-            const int nb = items_on() ? con_blocks() : parts_out ? n_parts_last : std::min(cdiv(n_owned, 256), (int)std::max<int64_t>(256, std::min<int64_t>(512, n_owned / 2048)));
-            double* cm_out = cm ? (parts_out ? cm_parts_last : cm_step.p + (size_t)half * 4 * 1024) : (double*)nullptr;
-            prof.begin(2, stream);
-            // the speeds for a check that the next step's force pass will measure (see resolve_track); evaluated behind the pass: a prune inside it makes the lists checkable again
-            const bool measure_mid = step != last && async_ok() && !held.trk_issued() && lp.check_due(step + 1, every);
-            if (measure_mid) trk_reserve(n_blocks);
-            if (th) thermo_step(step, step == last, nb, dt, cm_out, measure_mid);
-            else if (items_on()) con_launch(step == last ? 2 : 1, nb, dt, cm_out, measure_mid, nullptr);
-            else vv_mid_launch(cm, step == last, nb, dt, pending_cm.parts_arg(), pending_cm.n, cm_out, measure_mid);
-            prof.end(2, stream);
-            if (measure_mid) issue_track(nb, step + 1);   // the check of step + 1, read by resolve_track at step + 2
+            // behind the pass: a prune inside it makes the lists checkable again, so whether the launch measures is asked anew
+            StagePlan p = plan_stage(run, step_shape(step, step == last, remove_cm_every, n_parts_out), q, false);
+            // the sort permutes vel / frc with the atoms; Σ m v does not care.  Planned again behind it: the lists are new
+            if (p.refresh_behind) { fold_side_forces(); refresh(step); p = plan_stage(run, step_shape(step, step == last, remove_cm_every, n_parts_out), q, false); }
+            double* const cm_out = cm_out_of(p, half, cm_parts_last);
+            launch_stage(p, step, dt, cm_out);      // (a measured check of step + 1 is read by resolve_track at step + 2)
             if (step == last) held.run_ended(pend_a == nullptr && n_ghost == 0);
             step_closed(step != last);
-            if (cm && !parts_out && !th) { pending_cm.resum(cm_out, nb); half ^= 1; }      // (th: removed with the scale, nothing is pending)
+            if (p.repend) { pending_cm.resum(cm_out, p.nb); half ^= 1; }      // (th: removed with the scale, nothing is pending)
         }
     }
 
@@ -2562,7 +2573,7 @@ template <class T> class Engine final : public EngineBase {
         }
         thermo = ThermoP{};
         if (kind == THERMO_OFF) return;      // the context steps as one that never had a thermostat (the record of the last one stays readable)
-        thermo_info_dev.reserve(8); h_thermo.make(8); thermo_part.reserve(2 * 1024);      // (one partial per block of the close launch: at most 1024, as cm_step's halves)
+        thermo_info_dev.reserve(8); h_thermo.make(8); thermo_part.reserve(2 * CM_HALF_PARTS);      // (one partial per block of the close launch, as cm_step's halves)
         MHIP_HIP(hipMemsetAsync(thermo_info_dev.p, 0, 8 * sizeof(double), stream));
         for (double& x : thermo_host) x = 0;
         thermo.kind = kind; thermo.n_steps = n_steps; thermo.dof = dof; thermo.kT = kT; thermo.tau = tau; thermo.key = key; thermo.ctr1 = ctr1;
@@ -2570,10 +2581,11 @@ template <class T> class Engine final : public EngineBase {
     void thermostat_info(double* out8) override { for (int k = 0; k < 8; ++k) out8[k] = thermo_host[k]; }
     // the integrator stage of a step on which the thermostat applies: the close launch (closing kick, RATTLE, Σ m v and the thermostat partials), then the open
     // launch (λ from the partials, v = λ·(v − v_cm), first kick, drift, SHAKE, the check of step + 1) — or, on the run's last step, the flush of the scale
-    void thermo_step(int64_t step, bool last, int nb, double dt, double* cm_out, bool measure) {
+    void thermo_step(const StagePlan& p, int64_t step, double dt, double* cm_out) {
+        const bool last = p.form == StageForm::THERMO_LAST, items = p.con_mode >= 0, measure = p.measure; const int nb = p.nb;
         ThermoP P = thermo;
         P.step = step; P.ctr1 = thermo.ctr1 + (uint64_t)step; P.dt = dt; P.natoms = (uint64_t)cfg.n_atoms; P.info = thermo_info_dev.p;
-        if (items_on()) con_launch(2, nb, dt, cm_out, false, nullptr, &P, nullptr, thermo_part.p);
+        if (items) con_launch(p.con_mode, nb, dt, cm_out, false, nullptr, &P, nullptr, thermo_part.p);
         else {
             tr("k_vv_close");
             auto go = [&](auto kern) {
@@ -2587,9 +2599,9 @@ template <class T> class Engine final : public EngineBase {
             prof.end(2, stream);
             prof.begin(2, stream);
             tr("k_scale_vel");
-            hipLaunchKernelGGL(k_scale_vel<T>, dim3(std::min(cdiv(n_owned, 256), 1024)), dim3(256), 0, stream, n_owned, vel[cur].p, (const double*)cm_out, (const double*)thermo_part.p, nb, P,
+            hipLaunchKernelGGL(k_scale_vel<T>, dim3(stage_blocks(n_owned)), dim3(256), 0, stream, n_owned, vel[cur].p, (const double*)cm_out, (const double*)thermo_part.p, nb, P,
                                vs_on ? (const int32_t*)orig[cur].p : nullptr, (const uint8_t*)vs_flag.p);
-        } else if (items_on()) con_launch(0, nb, dt, nullptr, measure, nullptr, &P, thermo_part.p, nullptr, cm_out);
+        } else if (items) con_launch(0, nb, dt, nullptr, measure, nullptr, &P, thermo_part.p, nullptr, cm_out);
         else {
             tr("k_vv_open");
             hipLaunchKernelGGL(k_vv_open<T>, dim3(nb), dim3(256), 0, stream, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, T(dt), T(dt) / T(2), (const double*)cm_out, (const double*)thermo_part.p, nb, P, G,
@@ -2754,7 +2766,7 @@ template <class T> class Engine final : public EngineBase {
         if (parts18) std::copy(w, w + 18, parts18);
         if (n_not_converged) *n_not_converged = (int64_t)std::llround(w[18]);
     }
-    int con_blocks() const { return std::max(1, std::min(cdiv(con.n_items(), CON_BLOCK), 1024)); }      // (<= 1024: the Σ m v partials fit a half of cm_step)
+    int con_blocks() const { return item_blocks(con.n_items(), CON_BLOCK); }      // (<= CM_HALF_PARTS: the Σ m v partials fit a half of cm_step)
     void con_run_start() { MHIP_HIP(hipMemsetAsync(con_stat.p + 1, 0, sizeof(unsigned long long), stream)); }
     // the solver's counters travel with the run's closing synchronisation: no read-back inside the step loop
     void con_read_back() { MHIP_HIP(hipMemcpyAsync(h_con, con_stat.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream)); }
@@ -2933,50 +2945,36 @@ template <class T> class Engine final : public EngineBase {
         lp.cur_dt = dt;
         InRun guard_in_run(in_run);
         sites_run_start();                                                        // :1113-1114
-        const bool items = items_on();                                            // constraints or hosted sites: both stepped by k_con_step
-        InRun guard_lang(in_lang_fused); in_lang_fused = bonded.any() && pme.on() && fuse_gcv_env && !items;     // (constraints: k_con_step updates whole clusters, no force launch integrates)
-        InRun guard_lang_async(in_lang_async); in_lang_async = (in_lang_fused || items || (!bonded.any() && !pme.on() && fuse_step_env)) && !(andersen_prob > 0);
+        const bool items = items_on();                                            // constraints or hosted sites: both stepped by k_con_step (no force launch integrates then)
+        // a small system's step (bonded terms + PME): its last force launch — interpolation + bonded sums — runs the update as well (step_fused.h, k_gather_collect_vv<…, LANG>); the packed fp32
+        // one-type pass runs it in its epilogue (k_forces<…, STEP, ·, LANG>).  Every step of the run: a Langevin step is complete in itself, there is no closing half kick to keep a launch for
+        InLoop guard_loop(run, plan_run(run_shape(Loop::LANGEVIN)));
         if (first_step == 0 && remove_cm_every != 0) remove_cm();                 // :1115
         start_lists(first_step);                                                  // :1116
         const double vs = std::exp(-dt * friction);                               // :1091-1092
         StochP<T> P = stoch_params(kT, key, ctr1_0);
         P.dt = T(dt); P.dt_half = T(dt) / T(2); P.vel_scale = T(vs); P.noise_kt = std::sqrt(1.0 - vs * vs) * std::sqrt(kT);
-        const int nb = items ? con_blocks() : std::min(cdiv(n_owned, 256), 1024);
         if (items) con_run_start();
         int half = 0;
         for (int64_t step = first_step + 1; step <= first_step + n_steps; ++step) {
             // a check measured by the update launch of step s (the coordinates x_s it made) is read at the top of step s + 2, behind a whole step of queued work — the
             // scheme of mhip_vv_run, whose loop is one force pass ahead of this one (there the launch of step s makes x_(s+1)); a check left by a run before: at once
-            if (held.trk_issued() && (!in_lang_async || step > trk_step + 1)) resolve_track(step);
-            const bool cm = remove_cm_every != 0 && step % remove_cm_every == 0;
+            if (held.trk_issued() && resolve_due(run, step, trk_step)) resolve_track(step);
             P.ctr1 = ctr1_0 + (uint64_t)(step - first_step - 1);
-            // a small system's step (bonded terms + PME): its last force launch — interpolation + bonded sums — runs the update as well (step_fused.h, k_gather_collect_vv<…, LANG>),
-            // every step of the run: a Langevin step is complete in itself, there is no closing half kick to keep a launch for
-            const bool measure = in_lang_async && async_ok() && !held.trk_issued() && lp.check_due(step, every);      // the check refresh(step) below would make with a drained stream
-            PassReq req;
-            req.gcv = bonded.any() && pme.on() && !items; req.step = !bonded.any() && !pme.on() && !items; req.lang = &P; req.cm = cm; req.measure = measure; req.dt = dt;      // (step: the packed fp32 one-type pass runs the update in its epilogue, k_forces<…, STEP, ·, LANG>)
-            const PassRes res = step_forces(step, req);                          // :1173
-            if (res.step) {
-                after_fused_step(res, measure, step, cm);
-                apply_coupling(step);
-                if (lp.check_due(step, every)) refresh(step);
-                continue;
+            // measure: the check refresh(step) below would make with a drained stream
+            const StepShape s = step_shape(step, false, remove_cm_every);
+            const StepRequest q = plan_request(run, s);
+            const PassRes res = step_forces(step, pass_req(q, dt, &P));          // :1173
+            if (res.step) after_fused_step(res, q.measure, step, q.cm);
+            else {      // with items: kick, RATTLE, half drift, O-step, half drift, SHAKE per cluster (simulators.jl:1176-1201)
+                const StagePlan p = plan_stage(run, s, q, false);
+                double* const cm_out = cm_out_of(p, half, nullptr);             // the other half may still be read by this launch
+                launch_stage(p, step, dt, cm_out, &P);
+                drifted();
+                if (p.repend) { pending_cm.resum(cm_out, p.nb); half ^= 1; }     // :1204-1206, subtracted by the next consumer
             }
-            prof.begin(2, stream);
-            double* cm_out = cm ? cm_step.p + (size_t)half * 4 * 1024 : (double*)nullptr;   // the other half may still be read by this launch
-            if (items) {      // kick, RATTLE, half drift, O-step, half drift, SHAKE per cluster (simulators.jl:1176-1201)
-                if (measure) trk_reserve(n_blocks);
-                con_launch(3, nb, dt, cm_out, measure, &P);
-                if (measure) issue_track(nb, step);
-            } else
-            launch_langevin<T>(stream, nb, n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, orig[cur].p, P,
-                               pending_cm.vcm_arg(vcm.p), pending_cm.parts_arg(), pending_cm.n,
-                               cm_out, G, (const T4*)pend_a);      // (the side array of a small system's step is added by the update itself, as k_vv_mid does: no k_add_forces launch)
-            prof.end(2, stream);
-            drifted();
-            if (cm) { pending_cm.resum(cm_out, nb); half ^= 1; }   // :1204-1206, subtracted by the next consumer
             apply_coupling(step);                                                 // :1208
-            if (lp.check_due(step, every)) refresh(step);                            // :1211 — the next force pass prunes the fresh outer list
+            if (lp.check_due(step, every)) refresh(step);                         // :1211 — the next force pass prunes the fresh outer list
         }
         flush_cm();
         if (items) con_read_back();
