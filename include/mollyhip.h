@@ -307,6 +307,31 @@ int32_t mhip_rebuild(mhip_ctx* ctx, int64_t step_n);              /* force a nei
  *   CM removal and neighbour cadence as mhip_vv_run.  Step first_step + s (s = 1 …) uses ctr1 + s − 1 (:1189-1190). */
 int32_t mhip_langevin_run(mhip_ctx* ctx, int64_t first_step, int64_t n_steps, double dt, double kT, double friction,
                           int32_t remove_cm_every, uint64_t philox_key, uint64_t philox_ctr1);
+/* simulate!(sys, ::LangevinSplitting, n_steps) (simulators.jl:1212-1398): `splitting` is a sequence of A (drift), B (kick) and O (friction + noise)
+ * sub-steps, e.g. "BAOAB", "OBABO", "ABOBA"; sub-step j runs with dt / count(op_j, splitting) (:1305):
+ *   A: x += v·dt_eff; x = wrap(x)          B: v += dt_eff·(F/m)          O: v = exp(−a_i) v + sqrt(kT/m_i·(1 − exp(−2 a_i))) ξ,  a_i = friction·dt/(n_O·m_i)
+ * friction is the reference's mass-per-time quantity (:1282), NOT the inverse time of mhip_langevin_run: "BAOA" with friction = γ·m is that integrator.
+ * Which B computes forces is decided once per string (:1308-1324): the forces are known at the start unless an A follows the last B; an A voids them; a B
+ * that finds them void computes them at the coordinates of the moment.  When they are known at the start, the forces of the coordinates held are computed
+ * first (:1302), or taken from a run that ended on exactly this state (see mhip_vv_run); a string without a B computes none.
+ * The k-th O (0-based) of step first_step + s (s = 1 …) draws from philox_ctr1 + (s − 1)·n_O + k (:1355): a continued run passes philox_ctr1 + steps_done·n_O.
+ * An atom of mass 0 is left alone by B and O (:1272-1275) and moved by A.  End of every step: CM removal when step % remove_cm_every == 0 (:1365), the
+ * Andersen coupling if set (the reference has no coupling field here), the neighbour cadence (:1369).
+ * The engine's limits, not the reference's: at most 16 sub-steps; at most ONE force computation per step — a string such as "BABAB" (two) is
+ * MHIP_ERR_UNSUPPORTED; constraints and virtual sites are refused with MHIP_ERR_UNSUPPORTED (the reference ignores constraints with a warning), as is
+ * a rescaling thermostat; ghost atoms: MHIP_ERR_STATE (csrc/admit.h: the rows of mhip_langevin_run and mhip_vv_init).
+ * MHIP_ERR_INVALID: n_steps < 0, first_step < 0, dt not finite, kT < 0, friction < 0, splitting null, empty, longer than 16 or with another character. */
+int32_t mhip_splitting_run(mhip_ctx* ctx, int64_t first_step, int64_t n_steps, double dt, double kT, double friction,
+                           const char* splitting, int32_t remove_cm_every, uint64_t philox_key, uint64_t philox_ctr1);
+/* simulate!(sys, ::OverdampedLangevin, n_steps) (simulators.jl:1400-1489), Euler–Maruyama: per step (:1460-1476)
+ *   F = forces(x); x += ((F/m)/γ)·dt + sqrt(2 dt/γ)·sqrt(kT/m)·ξ; x = wrap(x);  neighbour cadence.  friction = γ is an inverse time, > 0 and finite.
+ * Step first_step + s draws ξ from (philox_key, philox_ctr1 + s − 1): one key and a counter that advances, where the reference draws a fresh pair from the
+ * host rng every step (random_velocities!, :1464).  Atoms of mass 0 do not move.  Velocities are never read by the dynamics; remove_CM_motion! (:1446,
+ * :1471) is applied to them ONCE per call that starts at step 0 or holds a due step, not once per due step: repeating it on unchanged velocities
+ * changes nothing but round-off.  The Andersen coupling, if set, is not applied (velocities play no part).  Admitted and refused as mhip_splitting_run;
+ * MHIP_ERR_INVALID: n_steps < 0, first_step < 0, dt not finite, kT < 0, friction not positive and finite. */
+int32_t mhip_overdamped_run(mhip_ctx* ctx, int64_t first_step, int64_t n_steps, double dt, double kT, double friction,
+                            int32_t remove_cm_every, uint64_t philox_key, uint64_t philox_ctr1);
 /* random_velocities!(sys, temp) (spatial.jl:803-831, random_velocities_kernel! kernels.jl:688-704): v_i = sqrt(kT/m_i) ξ_i */
 int32_t mhip_random_velocities(mhip_ctx* ctx, double kT, uint64_t philox_key, uint64_t philox_ctr1);
 /* One application of AndersenThermostat (coupling.jl:196-211, apply_andersen_coupling_kernel! kernels.jl:706-723): each atom is

@@ -136,3 +136,23 @@ function minimize!(log4::Matrix{Float64}, c::HipContext; first_step::Integer=0, 
                    c.ptr, first_step, max_steps, step_size, tol, constraint_bond_k, log4, out8))
     return out8
 end
+
+# mhip_splitting_run: simulate!(sys, ::LangevinSplitting, n) (simulators.jl:1255-1381) on the state the context holds.  splitting: 1 to 16 characters out of A, B, O
+# with at most one force computation per step (the engine's limits); friction is the reference's mass-per-time quantity; kT = temperature·k.  The k-th O
+# (0-based) of step first_step + s draws from philox_ctr1 + (s − 1)·n_O + k, so a continued run passes philox_ctr1 + steps_done·count('O', splitting).
+function splitting_run!(c::HipContext, splitting::AbstractString; first_step::Integer=0, n_steps::Integer, dt::Float64, kT::Float64, friction::Float64,
+                        remove_cm_every::Integer=1, philox_key::UInt64=UInt64(0), philox_ctr1::UInt64=UInt64(0))
+    check(c, ccall((:mhip_splitting_run, libmollyhip), Int32, (Ptr{Cvoid}, Int64, Int64, Float64, Float64, Float64, Cstring, Int32, UInt64, UInt64),
+                   c.ptr, first_step, n_steps, dt, kT, friction, String(splitting), remove_cm_every, philox_key, philox_ctr1))
+    return c
+end
+
+# mhip_overdamped_run: simulate!(sys, ::OverdampedLangevin, n) (simulators.jl:1426-1489), Euler–Maruyama; friction is an inverse time.  Step first_step + s draws
+# from (philox_key, philox_ctr1 + s − 1) — one key and a counter where the reference draws a fresh pair per step — and remove_CM_motion! is applied to the
+# (otherwise untouched) velocities once per call.
+function overdamped_run!(c::HipContext; first_step::Integer=0, n_steps::Integer, dt::Float64, kT::Float64, friction::Float64, remove_cm_every::Integer=1,
+                         philox_key::UInt64=UInt64(0), philox_ctr1::UInt64=UInt64(0))
+    check(c, ccall((:mhip_overdamped_run, libmollyhip), Int32, (Ptr{Cvoid}, Int64, Int64, Float64, Float64, Float64, Int32, UInt64, UInt64),
+                   c.ptr, first_step, n_steps, dt, kT, friction, remove_cm_every, philox_key, philox_ctr1))
+    return c
+end

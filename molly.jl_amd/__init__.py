@@ -12,6 +12,6 @@ from .api import (  # noqa: F401
     kinetic_energy, potential_energy, pressure, scalar_pressure, random_velocities, apply_coupling, remove_CM_motion, scalar_virial, simulate, temperature, total_energy, use_neighbors, virial,
     wrap_coords, optimize_launch_config, set_launch_config, MonteCarloBarostat, SteepestDescentMinimizer, scale_boundary, scale_coords, volume, BAR,
     DistanceConstraint, AngleConstraint, SHAKE_RATTLE, constraint_virial,
-    ImmediateThermostat, BerendsenThermostat, VelocityRescaleThermostat,
+    ImmediateThermostat, BerendsenThermostat, VelocityRescaleThermostat, LangevinSplitting, OverdampedLangevin,
     VirtualSite, OneParticleSite, TwoParticleAverageSite, ThreeParticleAverageSite, OutOfPlaneSite, place_virtual_sites,
 )

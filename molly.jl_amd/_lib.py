@@ -123,6 +123,8 @@ SIGNATURES = {
     "mhip_cm_momentum_dev": (_I32, [_P, _P]),
     "mhip_remove_cm_dev": (_I32, [_P, _P]),
     "mhip_langevin_run": (_I32, [_P, _I64, _I64, _D, _D, _D, _I32, C.c_uint64, C.c_uint64]),
+    "mhip_splitting_run": (_I32, [_P, _I64, _I64, _D, _D, _D, C.c_char_p, _I32, C.c_uint64, C.c_uint64]),
+    "mhip_overdamped_run": (_I32, [_P, _I64, _I64, _D, _D, _D, _I32, C.c_uint64, C.c_uint64]),
     "mhip_random_velocities": (_I32, [_P, _D, C.c_uint64, C.c_uint64]),
     "mhip_andersen": (_I32, [_P, _D, _D, C.c_uint64, C.c_uint64]),
     "mhip_set_andersen": (_I32, [_P, _D, _D, C.c_uint64]),

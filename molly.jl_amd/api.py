@@ -315,6 +315,23 @@ class Langevin:
         self.noise_scale = float(np.sqrt(1.0 - self.vel_scale ** 2))
 
 
+class LangevinSplitting:
+    """LangevinSplitting(; dt, temperature, friction, splitting, remove_CM_motion=1) (simulators.jl:1212-1253): a sequence of A (drift), B (kick) and O
+    (friction + noise) sub-steps, e.g. "BAOAB".  friction is a mass per time, as in the reference.  coupling: nothing or AndersenThermostat (this package's addition)."""
+
+    def __init__(self, dt, temperature, friction, splitting, remove_CM_motion=1, coupling=None):
+        self.dt, self.temperature, self.friction = float(dt), float(temperature), float(friction)
+        self.splitting, self.remove_CM_motion, self.coupling = str(splitting), int(remove_CM_motion), coupling
+
+
+class OverdampedLangevin:
+    """OverdampedLangevin(; dt, temperature, friction, remove_CM_motion=1) (simulators.jl:1400-1424): Euler–Maruyama; friction is an inverse time."""
+
+    def __init__(self, dt, temperature, friction, remove_CM_motion=1):
+        self.dt, self.temperature, self.friction = float(dt), float(temperature), float(friction)
+        self.remove_CM_motion, self.coupling = int(remove_CM_motion), None
+
+
 @dataclass
 class DistanceConstraint:
     """DistanceConstraint(i, j, dist) (constraints.jl:7-18): atoms i and j (0-based) held at distance dist (nm)"""
@@ -909,7 +926,8 @@ def _minimize_engine(sys, sim, init_step=0):
 
 
 def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
-    """simulate!(sys, sim, n_steps; init_step, rng) for VelocityVerlet (simulators.jl:547-668) and Langevin (:1099-1220), with
+    """simulate!(sys, sim, n_steps; init_step, rng) for VelocityVerlet (simulators.jl:547-668), Langevin (:1099-1220), LangevinSplitting (:1255-1381, coupling
+    nothing or AndersenThermostat) and OverdampedLangevin (:1426-1489); the first two with
     coupling nothing, AndersenThermostat, MonteCarloBarostat or a tuple of the two; VelocityVerlet also takes ImmediateThermostat, BerendsenThermostat and
     VelocityRescaleThermostat (alone or with the barostat), applied inside the device loop.  The step loop runs on the device; with a barostat it is cut at the
     multiples of barostat.n_steps, where apply_coupling! runs on the host side of the boundary with the engine's potential energies (the README's GPU
@@ -925,18 +943,19 @@ def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
         if init_step < 0:
             raise ValueError("init_step must be non-negative")
         return _minimize(sys, sim, init_step)
-    if not isinstance(sim, (VelocityVerlet, Langevin)):
+    if not isinstance(sim, (VelocityVerlet, Langevin, LangevinSplitting, OverdampedLangevin)):
         raise MollyHipError(-6, f"simulator {type(sim).__name__} is outside the hot-path scope")
     if n_steps is None:
         raise TypeError("simulate: n_steps is required for VelocityVerlet and Langevin")
+    splitting = isinstance(sim, (LangevinSplitting, OverdampedLangevin))
     couplings = sim.coupling if isinstance(sim.coupling, (tuple, list)) else (() if sim.coupling is None else (sim.coupling,))
     thermostat = barostat = rescale = None
     for c in couplings:
         if isinstance(c, AndersenThermostat) and thermostat is None:
             thermostat = c
-        elif type(c) in _RESCALE_KIND and rescale is None:
+        elif type(c) in _RESCALE_KIND and rescale is None and not splitting:
             rescale = c
-        elif isinstance(c, MonteCarloBarostat) and barostat is None:
+        elif isinstance(c, MonteCarloBarostat) and barostat is None and not splitting:
             barostat = c
         else:
             raise MollyHipError(-6, f"coupling {type(c).__name__} is outside the hot-path scope")
@@ -964,7 +983,14 @@ def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
                                              int(getattr(rescale, "n_steps", 1)), _df(sys), _rand_u64(rng), _rand_u64(rng)))
         if isinstance(sim, Langevin):
             key, ctr1 = _rand_u64(rng), _rand_u64(rng)             # simulators.jl:1149-1150
-        first, last = init_step, init_step + n_steps
+        if isinstance(sim, LangevinSplitting):                     # key, then ctr1 (simulators.jl:1291-1292); a splitting without an O draws nothing
+            key, ctr1 = (_rand_u64(rng), _rand_u64(rng)) if "O" in sim.splitting else (0, 0)
+            sys._check(L.mhip_splitting_run(sys._ctx, init_step, n_steps, sim.dt, BOLTZMANN * sim.temperature, sim.friction, sim.splitting.encode(),
+                                            int(sim.remove_CM_motion), key, ctr1))
+        if isinstance(sim, OverdampedLangevin):                    # one key and a counter that advances per step (mollyhip.h)
+            key, ctr1 = _rand_u64(rng), _rand_u64(rng)
+            sys._check(L.mhip_overdamped_run(sys._ctx, init_step, n_steps, sim.dt, BOLTZMANN * sim.temperature, sim.friction, int(sim.remove_CM_motion), key, ctr1))
+        first, last = init_step, init_step + (0 if splitting else n_steps)
         while first < last:
             nxt = last if barostat is None else min(last, (first // barostat.n_steps + 1) * barostat.n_steps)
             if isinstance(sim, Langevin):                         # ctr1 advances by one per step (simulators.jl:1190)

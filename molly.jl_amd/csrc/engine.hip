@@ -18,6 +18,7 @@
 #include "constraints.h"
 #include "virtual_sites.h"
 #include "minimize.h"
+#include "split_kernel.h"
 #include "pme.h"
 #include "step_fused.h"
 #include "hilbert.h"
@@ -116,6 +117,8 @@ struct EngineBase {
     virtual void virtual_site_info(int64_t*) = 0;
     virtual void domain_export(int64_t*, void*) = 0;
     virtual void minimize(int64_t, int64_t, double, double, double, double*, double*) = 0;
+    virtual void splitting_run(int64_t, int64_t, double, double, double, const char*, int, uint64_t, uint64_t) = 0;
+    virtual void overdamped_run(int64_t, int64_t, double, double, double, int, uint64_t, uint64_t) = 0;
 };
 
 // hipEvent stage timers (only active while profiling is on)
@@ -2983,6 +2986,102 @@ template <class T> class Engine final : public EngineBase {
         if (items) con_after_run();
     }
 
+    // ---- LangevinSplitting and OverdampedLangevin (simulators.jl:1212-1489; the plan: splitting.h, the kernel: splitting.hip) ------------------------
+    // Loops of their own beside vv_loop and langevin_run, with the default RunPlan as minimize has: no force launch integrates, no launch measures a list
+    // check (refresh at the cadence steps measures with a drained stream).  Per step one launch per segment of the string; a force pass, with the side array of
+    // a small system folded, in front of every segment that opens with a force-computing B.  A check that an earlier run left in flight is read before the
+    // loop: a search it asks for then carries first_step, and no search inside the loop is followed by a pass of the same step number on other coordinates.
+    void split_launch(const SplitProg<T>& P, double* cm_out) {
+        prof.begin(2, stream);
+        tr("k_split_segment");
+        launch_split_segment<T>(stream, stage_blocks(n_owned), n_owned, pos[cur].p, vel[cur].p, (const T4*)frc[cur].p, orig[cur].p, P, pending_cm.vcm_arg(vcm.p),
+                                pending_cm.parts_arg(), pending_cm.n, cm_out, G);
+        prof.end(2, stream);
+    }
+    void splitting_run(int64_t first_step, int64_t n_steps, double dt, double kT, double friction, const char* splitting, int remove_cm_every, uint64_t key,
+                       uint64_t ctr1_0) override {
+        admit(adm::LANGEVIN_RUN, 0, "mhip_splitting_run");      // a stochastic step loop on a single domain, no rescaling thermostat: the row of mhip_langevin_run …
+        admit(adm::VV_INIT, 0, "mhip_splitting_run");           // … whose launches know neither constraints nor sites: the row of mhip_vv_init
+        const SplitPlan sp = plan_splitting(splitting, dt);
+        if (!sp.ok) throw ApiError{MHIP_ERR_INVALID, "mhip_splitting_run: splitting must be 1 to 16 characters out of A, B and O"};
+        // (two passes of one step number on different coordinates: the list records — pass_step, the step of a prune, the outer list adopted at the step of its search — go by the step)
+        if (sp.n_force > 1) throw ApiError{MHIP_ERR_UNSUPPORTED, "mhip_splitting_run: a splitting that computes forces more than once per step (an A between two B twice) is not supported"};
+        const int every = rebuild_every();
+        lp.cur_dt = dt;
+        InRun guard_in_run(in_run);
+        if (first_step == 0 && remove_cm_every != 0) remove_cm();                 // simulators.jl:1296
+        if (held.trk_issued()) resolve_track(first_step);
+        // :1297-1302: neighbours, then the forces of the coordinates held — needed only when a B uses them before any A; kept from a run that ended on exactly this state
+        if (sp.forces_known_at_start && sp.n_b > 0) init_impl(first_step);
+        else { held.run_begins(); start_lists(first_step); }
+        SplitProg<T> seg[SPLIT_MAX_OPS];
+        for (int g = 0; g < sp.n_seg; ++g) {
+            SplitProg<T>& P = seg[g];
+            P = SplitProg<T>{};
+            for (int j = 0; j < SPLIT_MAX_OPS; ++j) { P.op[j] = SPLIT_A; P.dt[j] = T(0); P.ctr1[j] = 0; }
+            P.n = sp.seg[g].end - sp.seg[g].begin;
+            for (int j = 0; j < P.n; ++j) { P.op[j] = sp.ops[sp.seg[g].begin + j].op; P.dt[j] = T(sp.ops[sp.seg[g].begin + j].dt_eff); }
+            P.moves = sp.seg[g].has_a; P.kicks = sp.seg[g].has_b; P.noise = sp.seg[g].has_o;
+            P.o_rate = sp.n_o > 0 ? friction * dt / sp.n_o : 0.0; P.kT = kT; P.key = key; P.natoms = (uint64_t)cfg.n_atoms;
+        }
+        int half = 0;
+        const int64_t last = first_step + n_steps;
+        // the step's force pass sees the step's final coordinates (no A behind it): the cadence step's list upkeep then runs in front of the pass, on those coordinates,
+        // as vv_loop's does with the dual list — a prune it asks for happens where it was measured.  Else (an A behind the last B) at the end of the step, as langevin_run
+        const bool upkeep_in_front = sp.forces_known_at_start && sp.n_force == 1;
+        for (int64_t step = first_step + 1; step <= last; ++step) {
+            const bool cm = remove_cm_every != 0 && step % remove_cm_every == 0;  // :1365-1367
+            for (int g = 0; g < sp.n_seg; ++g) {
+                const SplitSegment& sg = sp.seg[g];
+                SplitProg<T>& P = seg[g];
+                for (int j = sg.begin; j < sg.end; ++j)                           // :1355, ctr1 advances per O sub-step
+                    if (sp.ops[j].op == SPLIT_O) P.ctr1[j - sg.begin] = ctr1_0 + (uint64_t)(step - first_step - 1) * (uint64_t)sp.n_o + (uint64_t)sp.ops[j].o_index;
+                if (sg.forces_first) {
+                    if (upkeep_in_front && lp.check_due(step, every)) refresh(step);                  // :1369, find_neighbors on x_step
+                    step_forces(step); fold_side_forces();                                            // :1392-1395
+                }
+                double* const cm_out = (cm && g == sp.n_seg - 1) ? cm_step_half(half) : nullptr;      // the other half may still be read by this launch
+                split_launch(P, cm_out);
+                step_closed(sg.has_a);
+                if (cm_out) { pending_cm.resum(cm_out, stage_blocks(n_owned)); half ^= 1; }           // subtracted by the next consumer
+            }
+            if (step == last) held.run_ended(held.frc_valid() && pend_a == nullptr);
+            apply_coupling(step);
+            if (!upkeep_in_front && lp.check_due(step, every)) refresh(step);     // :1369
+        }
+        flush_cm();
+        MHIP_HIP(hipGetLastError());
+        MHIP_HIP(hipStreamSynchronize(stream));
+    }
+    // Euler–Maruyama (:1460-1476): per step the forces of the coordinates held and one launch.  Velocities are never read by the dynamics: remove_CM_motion! is
+    // applied to them once, when the call has a due step (or starts at step 0), instead of once per due step — the repetitions change nothing but round-off.
+    void overdamped_run(int64_t first_step, int64_t n_steps, double dt, double kT, double gamma, int remove_cm_every, uint64_t key, uint64_t ctr1_0) override {
+        admit(adm::LANGEVIN_RUN, 0, "mhip_overdamped_run");
+        admit(adm::VV_INIT, 0, "mhip_overdamped_run");
+        const int every = rebuild_every();
+        lp.cur_dt = dt;
+        InRun guard_in_run(in_run);
+        const int64_t last = first_step + n_steps;
+        const bool cm_due = remove_cm_every != 0 && ((first_step == 0) || (last / remove_cm_every > first_step / remove_cm_every));      // :1446, :1471-1473
+        if (cm_due) remove_cm(); else flush_cm();
+        if (held.trk_issued()) resolve_track(first_step);
+        held.run_begins();
+        start_lists(first_step);                                                  // :1447
+        SplitProg<T> P{};
+        for (int j = 0; j < SPLIT_MAX_OPS; ++j) { P.op[j] = SPLIT_A; P.dt[j] = T(0); P.ctr1[j] = 0; }
+        P.n = 1; P.op[0] = SPLIT_OVERDAMPED; P.dt[0] = T(dt); P.moves = true;
+        P.kT = std::sqrt(kT); P.od_gamma = T(gamma); P.od_prefac = T(std::sqrt((2.0 / gamma) * dt)); P.key = key; P.natoms = (uint64_t)cfg.n_atoms;
+        for (int64_t step = first_step + 1; step <= last; ++step) {
+            P.ctr1[0] = ctr1_0 + (uint64_t)(step - first_step - 1);
+            step_forces(step); fold_side_forces();                                // :1461
+            split_launch(P, nullptr);                                             // :1464-1466
+            drifted();
+            if (lp.check_due(step, every)) refresh(step);                         // :1475
+        }
+        MHIP_HIP(hipGetLastError());
+        MHIP_HIP(hipStreamSynchronize(stream));
+    }
+
     int64_t export_neighbors(int32_t* oi, int32_t* oj, uint8_t* osp, int64_t capacity) override { return export_list(oi, oj, osp, capacity, true); }
     // now = false (statistics): count the pairs of the list in use, never search for it
     int64_t export_list(int32_t* oi, int32_t* oj, uint8_t* osp, int64_t capacity, bool now) {
@@ -3199,6 +3298,19 @@ int32_t mhip_langevin_run(mhip_ctx* ctx, int64_t first, int64_t n, double dt, do
     NEED_CTX(); return guard(ctx, [&] {
         if (first < 0 || n < 0 || !(dt > 0)) throw mhip::ApiError{MHIP_ERR_INVALID, "first_step and n_steps must be non-negative, dt positive"};
         ctx->e->langevin_run(first, n, dt, kT, friction, cm_every, key, ctr1); });
+}
+int32_t mhip_splitting_run(mhip_ctx* ctx, int64_t first, int64_t n, double dt, double kT, double friction, const char* splitting, int32_t cm_every, uint64_t key, uint64_t ctr1) {
+    NEED_CTX(); return guard(ctx, [&] {
+        if (first < 0 || n < 0 || !std::isfinite(dt)) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_splitting_run: first_step and n_steps must be non-negative, dt finite"};
+        if (!(kT >= 0) || !(friction >= 0)) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_splitting_run: temperature and friction must be non-negative"};
+        if (!mhip::plan_splitting(splitting, dt).ok) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_splitting_run: splitting must be 1 to 16 characters out of A, B and O"};
+        ctx->e->splitting_run(first, n, dt, kT, friction, splitting, cm_every, key, ctr1); });
+}
+int32_t mhip_overdamped_run(mhip_ctx* ctx, int64_t first, int64_t n, double dt, double kT, double friction, int32_t cm_every, uint64_t key, uint64_t ctr1) {
+    NEED_CTX(); return guard(ctx, [&] {
+        if (first < 0 || n < 0 || !std::isfinite(dt)) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_overdamped_run: first_step and n_steps must be non-negative, dt finite"};
+        if (!(kT >= 0) || !(friction > 0) || !std::isfinite(friction)) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_overdamped_run: temperature must be non-negative, friction positive and finite"};
+        ctx->e->overdamped_run(first, n, dt, kT, friction, cm_every, key, ctr1); });
 }
 int32_t mhip_random_velocities(mhip_ctx* ctx, double kT, uint64_t key, uint64_t ctr1) { NEED_CTX(); return guard(ctx, [&] { ctx->e->redraw_velocities(1, kT, 1.0, key, ctr1); }); }
 int32_t mhip_andersen(mhip_ctx* ctx, double kT, double prob, uint64_t key, uint64_t ctr1) { NEED_CTX(); return guard(ctx, [&] { ctx->e->redraw_velocities(0, kT, prob, key, ctr1); }); }
