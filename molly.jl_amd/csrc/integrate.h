@@ -327,8 +327,9 @@ __global__ void k_check_finite(int64_t n, const typename Vec<T>::T4* __restrict_
     int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (s >= n) return;
     auto p = pos[s]; auto v = vel[s]; auto f = frc[s];
-    T t = p.x + p.y + p.z + v.x + v.y + v.z + f.x + f.y + f.z;
-    if (!(t == t) || M<T>::fabs(t) > T(1e30)) atomicOr(&flags[FLAG_NAN], 1);
+    // every component on its own: in a sum +2e30 and −2e30 cancel, and nine components that are each in range add up to an alarm.  (NaN fails the comparison.)
+    auto ok = [](T a) { return M<T>::fabs(a) <= T(1e30); };
+    if (!(ok(p.x) && ok(p.y) && ok(p.z) && ok(v.x) && ok(v.y) && ok(v.z) && ok(f.x) && ok(f.y) && ok(f.z))) atomicOr(&flags[FLAG_NAN], 1);
 }
 
 }  // namespace mhip

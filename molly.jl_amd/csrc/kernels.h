@@ -183,7 +183,9 @@ __global__ void k_scatter_state(int64_t n_tot, int64_t n_owned, const int32_t* _
         int s = inv[o];
         if (xyz) {
             T c[3] = {xyz[3 * o], xyz[3 * o + 1], xyz[3 * o + 2]};
-            wrap_point(c[0], c[1], c[2], G);   // wrap_coords, simulators.jl:561
+            // wrap_coords, simulators.jl:561.  A magnitude beyond what mhip_check_finite accepts is stored as given: c − floor(c / L)·L of such a number is a
+            // finite multiple of its ulp, of no meaning, and would pass that check
+            if (M<T>::fabs(c[0]) <= T(1e30) && M<T>::fabs(c[1]) <= T(1e30) && M<T>::fabs(c[2]) <= T(1e30)) wrap_point(c[0], c[1], c[2], G);
             const auto p = pos[s];
             dx = !(p.x == c[0] && p.y == c[1] && p.z == c[2]);
             pos[s].x = c[0]; pos[s].y = c[1]; pos[s].z = c[2];
