@@ -46,7 +46,7 @@
  *   MOLLYHIP_PME_FFT=0|1           PME transforms through hipFFT never / always (default: meshes with more than 512 points on an axis); read whenever a context's PME is set up, mhip_stats.pme_fft says which
  *   MOLLYHIP_DEVICE_REPLAN=0       mhip_domain_run returns to the host planner for every re-plan (see mhip_set_domain)
  *   MOLLYHIP_HALO_WAITER=0         ranks sharing ONE device (tests): no one-workgroup waiter in front of a fused ghosted step; the blocks' own bounded waits order it, as across devices
- *   MOLLYHIP_PRUNE_LATE=0          inside mhip_domain_run a pruning pass of a ghosted sub-domain drains the stream for its summary instead of reading it behind an event
+ *   MOLLYHIP_PRUNE_LATE=0         inside mhip_domain_run a pruning pass of a ghosted sub-domain drains the stream for its summary instead of reading it behind an event
  * Host mirror only (the Python files of molly.jl_amd): MOLLYHIP_GHOST_MARGIN_PM, MOLLYHIP_ENGINE_LOOP, MOLLYHIP_HALO_FUSED, MOLLYHIP_HOST_PRUNE, MOLLYHIP_DIST_BACKEND,
  * MOLLYHIP_FORCE_DEVICE, MOLLYHIP_FORCE_DOMAIN (bench.py), MOLLYHIP_LIB_AB (another build of the library, tools/force_ab.py).  Builds with -DMHIP_STAMPS=1 only:
  * MOLLYHIP_DBG_TIMES, MOLLYHIP_DBG_DUMP (time stamps inside the block kernels).  Every other switch of rounds 1-5 lost its measurement and was removed with
@@ -613,6 +613,46 @@ typedef struct {
 int32_t mhip_set_domain(mhip_ctx* ctx, const mhip_domain_geometry* geometry, const int64_t* global_ids_dev);
 int32_t mhip_domain_info(mhip_ctx* ctx, int64_t* out8);
 int32_t mhip_domain_export(mhip_ctx* ctx, int64_t* global_ids_dev, void* params4_dev);
+
+
+/* ---- recording inside the step loops (≙ apply_loggers!, src/loggers.jl:44-56, called after every step by simulate!: src/simulators.jl:657, :1213) -----
+ * The reference's loggers read the state after every step; cutting a run at every logger interval costs a stream synchronisation, a copy of the whole
+ * state and one read-back per energy.  A context with a recorder takes what the loggers need on the device, inside mhip_vv_run and mhip_langevin_run,
+ * and keeps it in device memory until it is read.  Four channels, each with its own interval every[c] (0 = off) and capacity in records:
+ *
+ *   MHIP_REC_KE          one double: Σ ½ m v² of the owned atoms after the step's pending centre-of-mass removal — what mhip_kinetic_energy returns
+ *                        (≙ KineticEnergyLogger, and TemperatureLogger with 2·KE/(df·k) on the host: loggers.jl:96-102, 131-168)
+ *   MHIP_REC_PE          three doubles: pairwise, specific, general — what mhip_potential_energy(step), mhip_specific_potential_energy and
+ *                        mhip_general_potential_energy return for that state, 0 where the context has no such interaction (≙ PotentialEnergyLogger,
+ *                        TotalEnergyLogger: loggers.jl:170-214)
+ *   MHIP_REC_COORDS      3·n_atoms values of the context's precision, packed xyz in caller order, as mhip_get_state hands out coordinates
+ *                        (≙ CoordinatesLogger, loggers.jl:216-250)
+ *   MHIP_REC_VELOCITIES  the same for velocities (≙ VelocitiesLogger, loggers.jl:252-283)
+ *
+ * A run over the steps first + 1 … first + n records channel c at every step s of that range with s % every[c] == 0, in the state the reference's loggers
+ * see: after the closing kick, the centre-of-mass removal and the coupling of step s.  The step `first` itself is never recorded by a run (the reference's
+ * initial apply_loggers!, simulators.jl:571, is mhip_record_now).  Step numbering is global, so runs continued in chunks continue one history.  A record
+ * step is a chunk boundary without the host: the run gives the bits of the same run cut there and read through the energy and state entry points, and adds
+ * no read of device memory and no synchronisation of its own.  A run whose records do not fit is refused with MHIP_ERR_CAPACITY before anything is
+ * launched.  The loops that do not record — mhip_splitting_run, mhip_overdamped_run, mhip_domain_run, mhip_minimize, the mhip_vv_halo_* entry points —
+ * answer MHIP_ERR_UNSUPPORTED while a recorder is on; a caller that steps through mhip_vv_stage1 / mhip_vv_stage2 records with mhip_record_now.
+ *
+ *   mhip_set_record   : every4 / capacity4 per channel.  All intervals 0: off, the buffers are given back.  Always empties the history.
+ *                       MHIP_ERR_INVALID: a negative interval, a channel that is on with capacity < 1; MHIP_ERR_UNSUPPORTED: a context with ghosts, a
+ *                       domain plan, a halo plan or peers.
+ *   mhip_record_now   : record the state held under step number step_n, for the channels of the mask (bit c = channel c; loggers.jl:44-56 at the
+ *                       caller's own moment).  MHIP_ERR_INVALID: a channel without a buffer; MHIP_ERR_CAPACITY: a full channel.
+ *   mhip_record_info  : out16 = per channel { every, capacity, records held, step of the last record (−1: none) }
+ *   mhip_record_read  : records first … first + n − 1 of a channel (≙ values(logger), loggers.jl:96-102): doubles for KE and PE, the context's precision
+ *                       for frames, into host or device memory (mem_kind); steps_out (host, nullable) receives their step numbers.  A range beyond the
+ *                       records held: MHIP_ERR_INVALID.
+ *   mhip_record_clear : empties the history, keeps intervals and buffers */
+enum mhip_rec_channel { MHIP_REC_KE = 0, MHIP_REC_PE = 1, MHIP_REC_COORDS = 2, MHIP_REC_VELOCITIES = 3 };
+int32_t mhip_set_record(mhip_ctx* ctx, const int32_t* every4, const int64_t* capacity4);
+int32_t mhip_record_now(mhip_ctx* ctx, int64_t step_n, int32_t channel_mask);
+int32_t mhip_record_info(mhip_ctx* ctx, int64_t* out16);
+int32_t mhip_record_read(mhip_ctx* ctx, int32_t channel, int64_t first, int64_t n, int64_t* steps_out, void* values_out, int32_t mem_kind);
+int32_t mhip_record_clear(mhip_ctx* ctx);
 
 #ifdef __cplusplus
 }

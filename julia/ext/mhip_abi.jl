@@ -156,3 +156,41 @@ function overdamped_run!(c::HipContext; first_step::Integer=0, n_steps::Integer,
                    c.ptr, first_step, n_steps, dt, kT, friction, remove_cm_every, philox_key, philox_ctr1))
     return c
 end
+
+# ---- the recorder: what apply_loggers! (loggers.jl:44-56) reads of a step, taken inside mhip_vv_run / mhip_langevin_run and kept on the device --------------
+# Channels (0-based, as in mollyhip.h): 0 kinetic energy, 1 potential energy (pairwise, specific, general), 2 coordinates, 3 velocities.  The simulate! methods
+# of MollyHIPExt.jl still cut their runs at the logger intervals (run_chunks!): a caller who drives a HipContext directly records with these.
+# mhip_set_record: every / capacity per channel (every = 0: off); all off gives the buffers back; always empties the history.
+function set_record!(c::HipContext, every::Vector{Int32}, capacity::Vector{Int64})
+    (length(every) == 4 && length(capacity) == 4) || error("libmollyhip: set_record! takes four intervals and four capacities")
+    check(c, ccall((:mhip_set_record, libmollyhip), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ref{Int64}), c.ptr, every, capacity))
+    return c
+end
+
+# mhip_record_now: the state held, under step number step_n, for the channels of the mask (bit c = channel c) — the loggers before the first step
+# (simulators.jl:571) and between the calls of a run driven step by step
+function record_now!(c::HipContext, step_n::Integer, channel_mask::Integer)
+    check(c, ccall((:mhip_record_now, libmollyhip), Int32, (Ptr{Cvoid}, Int64, Int32), c.ptr, step_n, channel_mask))
+    return c
+end
+
+# mhip_record_info: per channel (every, capacity, records held, step of the last record or -1), a 4 × 4 matrix with one column per channel
+function record_info(c::HipContext)
+    out16 = zeros(Int64, 4, 4)
+    check(c, ccall((:mhip_record_info, libmollyhip), Int32, (Ptr{Cvoid}, Ref{Int64}), c.ptr, out16))
+    return out16
+end
+
+# mhip_record_read: records first … first + n − 1 (0-based) of a channel into host memory (≙ values(logger), loggers.jl:96-102): Float64 for channels 0 and 1
+# (1 and 3 values per record), the context's precision for the frames (3 × n_atoms per record).  Returns the records' step numbers.
+function record_read!(values::Array{T}, c::HipContext, channel::Integer, first::Integer, n::Integer) where {T<:Union{Float32, Float64}}
+    steps = zeros(Int64, n)
+    check(c, ccall((:mhip_record_read, libmollyhip), Int32, (Ptr{Cvoid}, Int32, Int64, Int64, Ref{Int64}, Ptr{Cvoid}, Int32), c.ptr, channel, first, n, steps, values, 0))
+    return steps
+end
+
+# mhip_record_clear: empties the history, keeps intervals and buffers
+function record_clear!(c::HipContext)
+    check(c, ccall((:mhip_record_clear, libmollyhip), Int32, (Ptr{Cvoid},), c.ptr))
+    return c
+end

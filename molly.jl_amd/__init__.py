@@ -14,4 +14,5 @@ from .api import (  # noqa: F401
     DistanceConstraint, AngleConstraint, SHAKE_RATTLE, constraint_virial,
     ImmediateThermostat, BerendsenThermostat, VelocityRescaleThermostat, LangevinSplitting, OverdampedLangevin,
     VirtualSite, OneParticleSite, TwoParticleAverageSite, ThreeParticleAverageSite, OutOfPlaneSite, place_virtual_sites,
+    TemperatureLogger, KineticEnergyLogger, PotentialEnergyLogger, TotalEnergyLogger, CoordinatesLogger, VelocitiesLogger, values,
 )

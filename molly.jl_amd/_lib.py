@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("MOLLYHIP_LIB_AB") or os.path.join(_HERE, "libmollyhip
 MEM_HOST, MEM_DEVICE = 0, 1
 CUTOFF_NONE, CUTOFF_DISTANCE, CUTOFF_SHIFTED_POTENTIAL, CUTOFF_SHIFTED_FORCE, CUTOFF_CUBIC_SPLINE, CUTOFF_POLYNOMIAL = range(6)
 COUL_NONE, COUL_PLAIN, COUL_REACTION_FIELD, COUL_EWALD_DIRECT = range(4)
+REC_KE, REC_PE, REC_COORDS, REC_VELOCITIES = range(4)      # the recorder's channels (mhip_set_record)
 
 STATUS = {0: "MHIP_OK", -1: "MHIP_ERR_INVALID", -2: "MHIP_ERR_HIP", -3: "MHIP_ERR_STATE", -4: "MHIP_ERR_CAPACITY",
           -5: "MHIP_ERR_NO_DEVICE", -6: "MHIP_ERR_UNSUPPORTED", -7: "MHIP_ERR_NAN"}
@@ -168,6 +169,11 @@ SIGNATURES = {
     "mhip_distribute_forces": (_I32, [_P, _P, _I32]),
     "mhip_virtual_site_info": (_I32, [_P, C.POINTER(_I64 * 8)]),
     "mhip_domain_export": (_I32, [_P, _P, _P]),
+    "mhip_set_record": (_I32, [_P, C.POINTER(_I32 * 4), C.POINTER(_I64 * 4)]),
+    "mhip_record_now": (_I32, [_P, _I64, _I32]),
+    "mhip_record_info": (_I32, [_P, C.POINTER(_I64 * 16)]),
+    "mhip_record_read": (_I32, [_P, _I32, _I64, _I64, _P, _P, _I32]),
+    "mhip_record_clear": (_I32, [_P]),
 }
 
 

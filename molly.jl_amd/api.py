@@ -415,6 +415,110 @@ def OutOfPlaneSite(atom_ind, atom_1, atom_2, atom_3, weight_12, weight_13, weigh
     return VirtualSite(4, atom_ind, atom_1, atom_2, atom_3, weight_12=weight_12, weight_13=weight_13, weight_cross=weight_cross)
 
 
+# ---- loggers (loggers.jl:131-283): what the engine's recorder takes inside the step loops (mhip_set_record), handed out as the reference's histories ----------
+class _Logger:
+    """a logger of the reference: records every n_steps steps (step_n % n_steps == 0, loggers.jl:98), values(logger) is its history; .steps are the step numbers"""
+    channels = ()
+
+    def __init__(self, n_steps):
+        if int(n_steps) != n_steps or int(n_steps) < 1:
+            raise ValueError(f"{type(self).__name__}: n_steps must be a positive integer, found {n_steps!r}")
+        self.n_steps = int(n_steps)
+        self.history = []
+        self.steps = []
+
+    def _value(self, rec, sys):
+        raise NotImplementedError
+
+
+class KineticEnergyLogger(_Logger):
+    """KineticEnergyLogger(n_steps) (loggers.jl:146-168)"""
+    channels = (_lib.REC_KE,)
+
+    def _value(self, rec, sys):
+        return rec[_lib.REC_KE]
+
+
+class TemperatureLogger(_Logger):
+    """TemperatureLogger(n_steps) (loggers.jl:131-144): 2·KE / (df·k) of the recorded kinetic energy (energy.jl:158-175)"""
+    channels = (_lib.REC_KE,)
+
+    def _value(self, rec, sys):
+        return 2 * rec[_lib.REC_KE] / (_df(sys) * BOLTZMANN)
+
+
+class PotentialEnergyLogger(_Logger):
+    """PotentialEnergyLogger(n_steps) (loggers.jl:170-192): pairwise + specific + general"""
+    channels = (_lib.REC_PE,)
+
+    def _value(self, rec, sys):
+        return _pe_total(rec[_lib.REC_PE])
+
+
+class TotalEnergyLogger(_Logger):
+    """TotalEnergyLogger(n_steps) (loggers.jl:194-214): kinetic + potential"""
+    channels = (_lib.REC_KE, _lib.REC_PE)
+
+    def _value(self, rec, sys):
+        return rec[_lib.REC_KE] + _pe_total(rec[_lib.REC_PE])
+
+
+class CoordinatesLogger(_Logger):
+    """CoordinatesLogger(n_steps) (loggers.jl:216-250): one (n, 3) array per record"""
+    channels = (_lib.REC_COORDS,)
+
+    def _value(self, rec, sys):
+        return rec[_lib.REC_COORDS]
+
+
+class VelocitiesLogger(_Logger):
+    """VelocitiesLogger(n_steps) (loggers.jl:252-283)"""
+    channels = (_lib.REC_VELOCITIES,)
+
+    def _value(self, rec, sys):
+        return rec[_lib.REC_VELOCITIES]
+
+
+def _pe_total(pe3):
+    """the sum potential_energy() forms: pairwise, then specific, then general, starting from 0.0"""
+    total = 0.0
+    for x in pe3:
+        total += float(x)
+    return total
+
+
+def values(logger):
+    """values(logger) (loggers.jl:85)"""
+    return logger.history
+
+
+def _check_run_loggers(run_loggers):
+    if not any(run_loggers is v for v in (True, False)) and run_loggers != "skipstart":      # loggers.jl:47-49
+        raise ValueError(f"run_loggers must be True, False or 'skipstart', found {run_loggers!r}")
+    return run_loggers
+
+
+def _record_plan(loggers, init_step, n_steps, run_loggers=True):
+    """What simulate() asks of the recorder for the steps init_step + 1 … init_step + n_steps: per channel the interval (the gcd of the n_steps of the loggers that
+    need it, 0: off) and the capacity (the multiples of the interval in that range, and one more where the initial apply_loggers! records it), and the mask of
+    that initial record (loggers.jl:50: always with True, with 'skipstart' only when init_step != 0; a logger records it when init_step % n_steps == 0)."""
+    _check_run_loggers(run_loggers)
+    every, capacity, start_mask = [0] * 4, [0] * 4, 0
+    if run_loggers is False:
+        return every, capacity, start_mask
+    at_start = run_loggers is True or init_step != 0
+    for lg in loggers:
+        for c in lg.channels:
+            every[c] = math.gcd(every[c], lg.n_steps)
+            if at_start and init_step % lg.n_steps == 0:
+                start_mask |= 1 << c
+    for c in range(4):
+        if every[c]:
+            capacity[c] = (init_step + n_steps) // every[c] - init_step // every[c] + ((start_mask >> c) & 1)
+            capacity[c] = max(capacity[c], 1)      # (a channel that is on needs room for one record)
+    return every, capacity, start_mask
+
+
 def _rng(rng):
     return rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
 
@@ -430,7 +534,7 @@ class System:
 
     def __init__(self, atoms=None, coords=None, boundary=None, velocities=None, pairwise_inters=(),
                  specific_inter_lists=(), neighbor_finder=None, dtype=np.float32, device_id=0,
-                 charge=None, sigma=None, eps=None, mass=None, general_inters=(), lam=None, constraints=(), virtual_sites=()):
+                 charge=None, sigma=None, eps=None, mass=None, general_inters=(), lam=None, constraints=(), virtual_sites=(), loggers=None):
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
             raise ValueError("dtype must be float32 or float64")
@@ -489,6 +593,11 @@ class System:
                         raise ValueError(f"atom {a} is a virtual site but is also in a constraint")
         self.total_mass = float(self.masses.sum(dtype=np.float64))
         self._pushed_atoms = False
+        self.loggers = dict(loggers) if loggers else {}      # name -> logger (types.jl:798-800); simulate() fills their histories from the engine's recorder
+        for name, lg in self.loggers.items():
+            if not isinstance(lg, _Logger):
+                raise MollyHipError(-6, f"logger {name!r} ({type(lg).__name__}) is outside the hot-path scope: the engine records kinetic and potential "
+                                        "energies, coordinates and velocities")
 
     def __len__(self):
         return len(self.coords)
@@ -925,14 +1034,52 @@ def _minimize_engine(sys, sim, init_step=0):
     return sys
 
 
-def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
+def _read_records(sys, L, every, replaced):
+    """the recorder's history, read once: per channel {step: value}; replaced: {(channel, step): value} taken on the host side (a barostat's move behind a record)"""
+    T = sys.dtype
+    info = (C.c_int64 * 16)()
+    sys._check(L.mhip_record_info(sys._ctx, C.byref(info)))
+    out = {}
+    for c in range(4):
+        if not every[c]:
+            continue
+        n = int(info[4 * c + 2])
+        steps = np.zeros(n, np.int64)
+        shape = {_lib.REC_KE: (n,), _lib.REC_PE: (n, 3)}.get(c, (n, len(sys), 3))
+        vals = np.zeros(shape, T if c >= _lib.REC_COORDS else np.float64)
+        if n:
+            sys._check(L.mhip_record_read(sys._ctx, c, 0, n, sys._ptr(steps), sys._ptr(vals), _lib.MEM_HOST))
+        vals = vals.tolist() if c == _lib.REC_KE else vals      # (python floats for the scalar channel: the histories hold what kinetic_energy() returns)
+        out[c] = {int(s): replaced.get((c, int(s)), vals[k]) for k, s in enumerate(steps)}
+    return out
+
+
+def _fill_loggers(sys, records):
+    """append to each logger the records whose step is a multiple of its own n_steps (loggers.jl:98), in step order"""
+    for lg in sys.loggers.values():
+        for s in sorted(records[lg.channels[0]]):
+            if s % lg.n_steps == 0 and all(s in records[c] for c in lg.channels):
+                v = lg._value({c: records[c][s] for c in lg.channels}, sys)
+                lg.history.append(v.copy() if isinstance(v, np.ndarray) else v)
+                lg.steps.append(s)
+
+
+def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None, run_loggers=True):
     """simulate!(sys, sim, n_steps; init_step, rng) for VelocityVerlet (simulators.jl:547-668), Langevin (:1099-1220), LangevinSplitting (:1255-1381, coupling
     nothing or AndersenThermostat) and OverdampedLangevin (:1426-1489); the first two with
     coupling nothing, AndersenThermostat, MonteCarloBarostat or a tuple of the two; VelocityVerlet also takes ImmediateThermostat, BerendsenThermostat and
     VelocityRescaleThermostat (alone or with the barostat), applied inside the device loop.  The step loop runs on the device; with a barostat it is cut at the
     multiples of barostat.n_steps, where apply_coupling! runs on the host side of the boundary with the engine's potential energies (the README's GPU
     example: Langevin + MonteCarloBarostat).  Coordinates and velocities come back when the call returns.  rng: a numpy Generator or a seed; as in the
-    reference it supplies the Philox key / counter words and the barostat's uniform numbers."""
+    reference it supplies the Philox key / counter words and the barostat's uniform numbers.
+    sys.loggers (apply_loggers!, loggers.jl:44-56; run_loggers True, False or "skipstart"): VelocityVerlet and Langevin record inside the device loop — the
+    engine's recorder is set for the call (one interval per channel: the gcd of the loggers that need it), the initial record is taken, the run is made as
+    without loggers, the channels are read once at the end and each logger gets the records at the multiples of its own n_steps.  A record at a step on which
+    the barostat applies is taken again behind its move, as the reference logs behind apply_coupling!.  The other simulators refuse loggers."""
+    _check_run_loggers(run_loggers)
+    recording = bool(sys.loggers) and run_loggers is not False
+    if recording and isinstance(sim, (SteepestDescentMinimizer, LangevinSplitting, OverdampedLangevin)):
+        raise MollyHipError(-6, f"loggers are recorded inside the VelocityVerlet and Langevin loops only: {type(sim).__name__} does not record (run_loggers=False runs it without them)")
     if isinstance(sim, SteepestDescentMinimizer) and sim.engine_loop:
         if init_step < 0:
             raise ValueError("init_step must be non-negative")
@@ -977,7 +1124,13 @@ def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
     sys.push_state(velocities=True)
     if thermostat is not None:
         sys._check(L.mhip_set_andersen(sys._ctx, BOLTZMANN * float(thermostat.temperature), float(sim.dt) / float(thermostat.coupling_const), _rand_u64(rng)))
+    every, replaced = [0] * 4, {}
     try:
+        if recording:
+            every, capacity, start_mask = _record_plan(sys.loggers.values(), init_step, n_steps, run_loggers)
+            sys._check(L.mhip_set_record(sys._ctx, C.byref((C.c_int32 * 4)(*every)), C.byref((C.c_int64 * 4)(*capacity))))
+            if start_mask:                                         # the loggers before the first step (simulators.jl:571, 1120)
+                sys._check(L.mhip_record_now(sys._ctx, init_step, start_mask))
         if rescale is not None:      # key and ctr1 once per call; application s draws from (key, ctr1 + s) on the device
             sys._check(L.mhip_set_thermostat(sys._ctx, _RESCALE_KIND[type(rescale)], BOLTZMANN * float(rescale.temperature), float(getattr(rescale, "coupling_const", 1.0)),
                                              int(getattr(rescale, "n_steps", 1)), _df(sys), _rand_u64(rng), _rand_u64(rng)))
@@ -1002,8 +1155,16 @@ def simulate(sys, sim, n_steps=None, init_step=0, check_nans=False, rng=None):
                 sys.pull_state()
                 _apply_mc_barostat(sys, barostat, nxt, rng)
                 sys.push_state(velocities=True)                   # the accepted box and coordinates, or the old ones back after a rejected trial
+                if every[_lib.REC_COORDS] and nxt % every[_lib.REC_COORDS] == 0:      # the loggers run behind the coupling (simulators.jl:630, 657)
+                    replaced[(_lib.REC_COORDS, nxt)] = sys.coords.copy()
+                if every[_lib.REC_PE] and nxt % every[_lib.REC_PE] == 0:
+                    replaced[(_lib.REC_PE, nxt)] = [potential_energy(sys, nxt, pairwise=k == 0, specific=k == 1, general=k == 2) for k in range(3)]
             first = nxt
+        if recording:
+            _fill_loggers(sys, _read_records(sys, L, every, replaced))
     finally:
+        if recording:
+            sys._check(L.mhip_set_record(sys._ctx, C.byref((C.c_int32 * 4)()), C.byref((C.c_int64 * 4)())))
         if thermostat is not None:
             sys._check(L.mhip_set_andersen(sys._ctx, 0.0, 0.0, 0))
         if rescale is not None:

@@ -24,6 +24,8 @@
 #include "hilbert.h"
 #include "kernels.h"
 #include "integrate.h"
+#include "record.h"
+#include "record_plan.h"
 #include "list_policy.h"
 #include "step_plan.h"
 #include "held.h"
@@ -119,6 +121,12 @@ struct EngineBase {
     virtual void minimize(int64_t, int64_t, double, double, double, double*, double*) = 0;
     virtual void splitting_run(int64_t, int64_t, double, double, double, const char*, int, uint64_t, uint64_t) = 0;
     virtual void overdamped_run(int64_t, int64_t, double, double, double, int, uint64_t, uint64_t) = 0;
+    virtual void set_record(const int32_t*, const int64_t*) = 0;
+    virtual void record_now(int64_t, int32_t) = 0;
+    virtual void record_info(int64_t*) = 0;
+    virtual void record_read(int32_t, int64_t, int64_t, int64_t*, void*, int) = 0;
+    virtual void record_clear() = 0;
+    virtual void no_recorder(const char*) const = 0;
 };
 
 // hipEvent stage timers (only active while profiling is on)
@@ -2498,16 +2506,130 @@ template <class T> class Engine final : public EngineBase {
         if (p.measure) issue_track(p.nb, p.check_step);
     }
 
+    // ---- the recorder (record.h, record_plan.h): what apply_loggers! reads of a step (loggers.jl:44-56), kept in device memory until the run is over ----------
+    // KE: Σ ½ m v² (loggers.jl:131-168 with 96-102 on top); PE: pairwise, specific, general (:170-214); frames: coordinates and velocities in caller order
+    // (:216-283).  A record costs no host read and no synchronisation: the sums are folded into their slots by k_sum_double, the step numbers are the host's own.
+    static constexpr int REC_STATE_CHANNELS = (1 << MHIP_REC_KE) | (1 << MHIP_REC_COORDS) | (1 << MHIP_REC_VELOCITIES);      // what k_record takes in one pass
+    struct Recorder {
+        RecEvery ev{}; RecCount cap{}, used{};
+        std::vector<int64_t> steps[REC_CHANNELS];
+        DBuf<double> ke, pe; DBuf<T> xs, vs;
+        bool on() const { return rec_any(ev); }
+    } rec;
+    void no_recorder(const char* name) const override {
+        if (rec.on()) throw ApiError{MHIP_ERR_UNSUPPORTED, std::string(name) + ": refused while the recorder is on (mhip_set_record): it records single domains, inside mhip_vv_run and mhip_langevin_run only"};
+    }
+    size_t rec_width(int c) const { return c == MHIP_REC_KE ? 1 : c == MHIP_REC_PE ? 3 : 3 * (size_t)cfg.n_atoms; }
+    void set_record(const int32_t* every, const int64_t* capacity) override {
+        if (!every || !capacity) throw ApiError{MHIP_ERR_INVALID, "mhip_set_record: null intervals or capacities"};
+        bool any = false;
+        for (int c = 0; c < REC_CHANNELS; ++c) {
+            if (every[c] < 0) throw ApiError{MHIP_ERR_INVALID, "mhip_set_record: negative interval"};
+            if (every[c] > 0 && capacity[c] < 1) throw ApiError{MHIP_ERR_INVALID, "mhip_set_record: a channel that is on needs a capacity of at least one record"};
+            any = any || every[c] > 0;
+        }
+        bool peers = xf.region.p != nullptr || xf.world > 1;
+        if (any && (n_ghost > 0 || dom.ready || hp_set || peers))
+            throw ApiError{MHIP_ERR_UNSUPPORTED, "mhip_set_record: the recorder records single domains only (this context has ghosts, a domain plan, a halo plan or peers)"};
+        MHIP_HIP(hipStreamSynchronize(stream));      // (a record launch may still be writing the buffers given back here)
+        Recorder fresh;
+        for (int c = 0; c < REC_CHANNELS; ++c) if (every[c] > 0) { fresh.ev.every[c] = every[c]; fresh.cap.n[c] = capacity[c]; }
+        fresh.ke.alloc((size_t)fresh.cap.n[MHIP_REC_KE]); fresh.pe.alloc(3 * (size_t)fresh.cap.n[MHIP_REC_PE]);
+        fresh.xs.alloc(rec_width(MHIP_REC_COORDS) * (size_t)fresh.cap.n[MHIP_REC_COORDS]); fresh.vs.alloc(rec_width(MHIP_REC_VELOCITIES) * (size_t)fresh.cap.n[MHIP_REC_VELOCITIES]);
+        rec = std::move(fresh);                      // (an allocation that failed has thrown: the recorder stands as it was)
+    }
+    void record_clear() override { for (int c = 0; c < REC_CHANNELS; ++c) { rec.used.n[c] = 0; rec.steps[c].clear(); } }
+    void record_info(int64_t* out16) override {
+        for (int c = 0; c < REC_CHANNELS; ++c) {
+            out16[4 * c] = rec.ev.every[c]; out16[4 * c + 1] = rec.cap.n[c]; out16[4 * c + 2] = rec.used.n[c];
+            out16[4 * c + 3] = rec.steps[c].empty() ? -1 : rec.steps[c].back();
+        }
+    }
+    // refused before anything is launched: the records of the run (first, n) must fit
+    void record_room(int64_t first, int64_t n, const char* name) const {
+        if (rec.on() && !rec_fits(rec.ev, first, n, rec.used, rec.cap))
+            throw ApiError{MHIP_ERR_CAPACITY, std::string(name) + ": the records of this run do not fit the recorder's free capacity (mhip_set_record, mhip_record_clear)"};
+    }
+    void record_now(int64_t step_n, int32_t mask) override {
+        if (mask < 0 || mask >= (1 << REC_CHANNELS)) throw ApiError{MHIP_ERR_INVALID, "mhip_record_now: the mask names channels 0 .. 3"};
+        for (int c = 0; c < REC_CHANNELS; ++c) if ((mask >> c) & 1) {
+            if (rec.ev.every[c] <= 0) throw ApiError{MHIP_ERR_INVALID, "mhip_record_now: the mask names a channel that has no buffer (mhip_set_record)"};
+        }
+        for (int c = 0; c < REC_CHANNELS; ++c) if (((mask >> c) & 1) && rec.used.n[c] >= rec.cap.n[c]) throw ApiError{MHIP_ERR_CAPACITY, "mhip_record_now: the channel is full"};
+        if (mask & REC_STATE_CHANNELS) record_at(step_n, mask & REC_STATE_CHANNELS);
+        if (mask & (1 << MHIP_REC_PE)) record_at(step_n, 1 << MHIP_REC_PE);
+        MHIP_HIP(hipGetLastError());
+    }
+    // The launches of one record; room has been checked.  KE and frames: one k_record pass (which applies the pending Σ m v removal, as any reader of the
+    // velocities does).  PE: the three energy entry points' own launches, their sums folded into the slot instead of being read back.
+    void record_at(int64_t step, int mask) {
+        if (mask & REC_STATE_CHANNELS) {
+            const bool ke = mask & (1 << MHIP_REC_KE), fx = mask & (1 << MHIP_REC_COORDS), fv = mask & (1 << MHIP_REC_VELOCITIES);
+            const int nb = cdiv(n_owned, 256);
+            if (ke) red_part.reserve(nb);
+            T* const frame_x = fx ? rec.xs.p + rec_width(MHIP_REC_COORDS) * (size_t)rec.used.n[MHIP_REC_COORDS] : (T*)nullptr;
+            T* const frame_v = fv ? rec.vs.p + rec_width(MHIP_REC_VELOCITIES) * (size_t)rec.used.n[MHIP_REC_VELOCITIES] : (T*)nullptr;
+            tr("k_record");      // (the frames by its scatter-write through orig: a gather-read through inv in a launch of its own behind it measured slower)
+            hipLaunchKernelGGL(k_record<T>, dim3(nb), dim3(256), 0, stream, n_owned, (const T4*)pos[cur].p, vel[cur].p, pending_cm.vcm_arg(vcm.p), pending_cm.parts_arg(), pending_cm.n,
+                               (const int32_t*)orig[cur].p, vs_on ? (const uint8_t*)vs_flag.p : (const uint8_t*)nullptr, ke ? red_part.p : (double*)nullptr, frame_x, frame_v);
+            pending_cm.none();
+            if (ke) hipLaunchKernelGGL(k_sum_double, dim3(1), dim3(256), 0, stream, nb, (const double*)red_part.p, rec.ke.p + rec.used.n[MHIP_REC_KE]);
+            MHIP_HIP(hipGetLastError());
+        }
+        if (mask & (1 << MHIP_REC_PE)) {
+            double* const slot = rec.pe.p + 3 * (size_t)rec.used.n[MHIP_REC_PE];
+            MHIP_HIP(hipMemsetAsync(slot, 0, 3 * sizeof(double), stream));      // (0 where the context has no such interaction)
+            ensure_built(step);                                                  // mhip_potential_energy(step)
+            energy_pass();
+            hipLaunchKernelGGL(k_sum_double, dim3(1), dim3(256), 0, stream, n_blocks, (const double*)red_part.p, slot);
+            admit(adm::SPECIFIC_ENERGY);                                         // mhip_specific_potential_energy
+            const int n_part = bonded.launch_energy(stream, G, I, pos[cur].p, inv.p, red_part);
+            if (n_part) hipLaunchKernelGGL(k_sum_double, dim3(1), dim3(256), 0, stream, n_part, (const double*)red_part.p, slot + 1);
+            admit(adm::GENERAL_ENERGY);                                          // mhip_general_potential_energy
+            if (pme.on()) {
+                const int nb = pme_energy_parts();
+                hipLaunchKernelGGL(k_record_recip, dim3(1), dim3(256), 0, stream, nb, (const double*)red_part.p, pme_energy_const(), slot + 2);
+            }
+            MHIP_HIP(hipGetLastError());
+        }
+        for (int c = 0; c < REC_CHANNELS; ++c) if ((mask >> c) & 1) { rec.steps[c].push_back(step); ++rec.used.n[c]; }
+    }
+    void record_read(int32_t channel, int64_t first, int64_t n, int64_t* steps_out, void* values_out, int mem_kind) override {
+        if (channel < 0 || channel >= REC_CHANNELS) throw ApiError{MHIP_ERR_INVALID, "mhip_record_read: channel must be 0 .. 3"};
+        if (first < 0 || n < 0 || first > rec.used.n[channel] || n > rec.used.n[channel] - first) throw ApiError{MHIP_ERR_INVALID, "mhip_record_read: records out of range"};
+        if (mem_kind != MHIP_MEM_HOST && mem_kind != MHIP_MEM_DEVICE) throw ApiError{MHIP_ERR_INVALID, "mhip_record_read: unknown mem_kind"};
+        if (steps_out) std::copy(rec.steps[channel].begin() + first, rec.steps[channel].begin() + first + n, steps_out);
+        if (!values_out || n == 0) return;
+        const bool frame = channel >= MHIP_REC_COORDS;
+        const size_t w = rec_width(channel) * (frame ? sizeof(T) : sizeof(double));
+        const char* src = channel == MHIP_REC_KE ? (const char*)rec.ke.p : channel == MHIP_REC_PE ? (const char*)rec.pe.p : channel == MHIP_REC_COORDS ? (const char*)rec.xs.p : (const char*)rec.vs.p;
+        MHIP_HIP(hipMemcpyAsync(values_out, src + w * (size_t)first, w * (size_t)n, mem_kind == MHIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
+        if (mem_kind == MHIP_MEM_HOST) MHIP_HIP(hipStreamSynchronize(stream));
+    }
+
     void vv_run(int64_t first_step, int64_t n_steps, double dt, int remove_cm_every) override {
         admit(adm::VV_RUN);      // (ghosted domains are driven by the halo entry points or mhip_domain_run)
-        lp.cur_dt = dt;
-        InRun guard_in_run(in_run);
-        sites_run_start();                                                        // :561-562
-        if (first_step == 0 && remove_cm_every != 0) remove_cm();                 // simulators.jl:563
-        init_impl(first_step);                                                    // :564-571
-        if (items_on()) con_run_start();
-        vv_loop(first_step, n_steps, dt, remove_cm_every, nullptr, 0);
-        flush_cm();
+        record_room(first_step, n_steps, "mhip_vv_run");
+        // With the recorder on the run is walked as segments that end at the record steps (record_plan.h); a record step is a chunk boundary without the host:
+        // its last step is planned as a run's last, the record launches run, the next segment is entered as a chunk is.  Without it: one segment.
+        const int64_t last = first_step + n_steps;
+        for (int64_t at = first_step;;) {
+            const int64_t stop = rec.on() ? std::min(rec_next_step(rec.ev, at + 1), last) : last;
+            {
+                lp.cur_dt = dt;
+                InRun guard_in_run(in_run);
+                sites_run_start();                                                    // :561-562
+                if (at == 0 && remove_cm_every != 0) remove_cm();                     // simulators.jl:563
+                init_impl(at);                                                        // :564-571
+                if (items_on()) con_run_start();
+                vv_loop(at, stop - at, dt, remove_cm_every, nullptr, 0);
+            }
+            const int mask = rec.on() && stop > at ? rec_mask(rec.ev, stop) : 0;
+            if (mask & REC_STATE_CHANNELS) record_at(stop, mask & REC_STATE_CHANNELS); else flush_cm();      // (k_record flushes on its way)
+            if (mask & (1 << MHIP_REC_PE)) record_at(stop, 1 << MHIP_REC_PE);                                 // apply_loggers!, simulators.jl:657
+            if (stop >= last) break;
+            at = stop;
+        }
         if (items_on()) con_read_back();
         if (thermo_on()) MHIP_HIP(hipMemcpyAsync(h_thermo, thermo_info_dev.p, 8 * sizeof(double), hipMemcpyDeviceToHost, stream));      // (travels with the closing synchronisation, as the solver's counters do)
         MHIP_HIP(hipGetLastError());
@@ -2944,6 +3066,24 @@ template <class T> class Engine final : public EngineBase {
     void langevin_run(int64_t first_step, int64_t n_steps, double dt, double kT, double friction, int remove_cm_every, uint64_t key, uint64_t ctr1_0) override {
         admit(adm::LANGEVIN_RUN);      // (the rescaling thermostats are a coupling of mhip_vv_run)
         if (!(kT >= 0) || !(friction >= 0)) throw ApiError{MHIP_ERR_INVALID, "temperature and friction must be non-negative"};
+        record_room(first_step, n_steps, "mhip_langevin_run");
+        // the recorder's segments, as in vv_run: each is entered as a chunk is, with the counter of its first step
+        const int64_t last = first_step + n_steps;
+        for (int64_t at = first_step;;) {
+            const int64_t stop = rec.on() ? std::min(rec_next_step(rec.ev, at + 1), last) : last;
+            langevin_segment(at, stop - at, dt, kT, friction, remove_cm_every, key, ctr1_0 + (uint64_t)(at - first_step));
+            const int mask = rec.on() && stop > at ? rec_mask(rec.ev, stop) : 0;
+            if (mask & REC_STATE_CHANNELS) record_at(stop, mask & REC_STATE_CHANNELS); else flush_cm();      // (k_record flushes on its way)
+            if (mask & (1 << MHIP_REC_PE)) record_at(stop, 1 << MHIP_REC_PE);                                 // apply_loggers!, simulators.jl:1213
+            if (stop >= last) break;
+            at = stop;
+        }
+        if (items_on()) con_read_back();
+        MHIP_HIP(hipGetLastError());
+        MHIP_HIP(hipStreamSynchronize(stream));
+        if (items_on()) con_after_run();
+    }
+    void langevin_segment(int64_t first_step, int64_t n_steps, double dt, double kT, double friction, int remove_cm_every, uint64_t key, uint64_t ctr1_0) {
         const int every = rebuild_every();
         lp.cur_dt = dt;
         InRun guard_in_run(in_run);
@@ -2979,11 +3119,6 @@ template <class T> class Engine final : public EngineBase {
             apply_coupling(step);                                                 // :1208
             if (lp.check_due(step, every)) refresh(step);                         // :1211 — the next force pass prunes the fresh outer list
         }
-        flush_cm();
-        if (items) con_read_back();
-        MHIP_HIP(hipGetLastError());
-        MHIP_HIP(hipStreamSynchronize(stream));
-        if (items) con_after_run();
     }
 
     // ---- LangevinSplitting and OverdampedLangevin (simulators.jl:1212-1489; the plan: splitting.h, the kernel: splitting.hip) ------------------------
@@ -3230,7 +3365,7 @@ const char* mhip_last_error(const mhip_ctx* ctx) { return (ctx && ctx->e) ? ctx-
 int32_t mhip_set_stream(mhip_ctx* ctx, void* s) { NEED_CTX(); return guard(ctx, [&] { ctx->e->set_stream(s); }); }
 int32_t mhip_synchronize(mhip_ctx* ctx) { NEED_CTX(); return guard(ctx, [&] { ctx->e->synchronize(); }); }
 int32_t mhip_set_profiling(mhip_ctx* ctx, int32_t on) { NEED_CTX(); return guard(ctx, [&] { ctx->e->set_profiling(on != 0); }); }
-int32_t mhip_set_atom_counts(mhip_ctx* ctx, int64_t no, int64_t ng) { NEED_CTX(); return guard(ctx, [&] { ctx->e->set_atom_counts(no, ng); }); }
+int32_t mhip_set_atom_counts(mhip_ctx* ctx, int64_t no, int64_t ng) { NEED_CTX(); return guard(ctx, [&] { if (ng > 0) ctx->e->no_recorder("mhip_set_atom_counts with ghosts"); ctx->e->set_atom_counts(no, ng); }); }
 int32_t mhip_set_atoms(mhip_ctx* ctx, const void* q, const void* s, const void* e, const void* m, const void* l, int32_t mk) {
     NEED_CTX(); return guard(ctx, [&] { ctx->e->set_atoms(q, s, e, m, l, mk); });
 }
@@ -3271,6 +3406,7 @@ int32_t mhip_rebuild(mhip_ctx* ctx, int64_t step_n) { NEED_CTX(); return guard(c
 int32_t mhip_minimize(mhip_ctx* ctx, int64_t first, int64_t max_steps, double step_size, double tol, double cbk, double* log4, double* out8) {
     NEED_CTX();
     return guard(ctx, [&] {
+        ctx->e->no_recorder("mhip_minimize");
         if (max_steps < 0 || first < 0) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_minimize: first_step and max_steps must be >= 0"};
         if (!(step_size > 0) || !std::isfinite(step_size)) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_minimize: step_size must be positive and finite"};
         if (std::isnan(tol)) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_minimize: tol is NaN"};
@@ -3301,6 +3437,7 @@ int32_t mhip_langevin_run(mhip_ctx* ctx, int64_t first, int64_t n, double dt, do
 }
 int32_t mhip_splitting_run(mhip_ctx* ctx, int64_t first, int64_t n, double dt, double kT, double friction, const char* splitting, int32_t cm_every, uint64_t key, uint64_t ctr1) {
     NEED_CTX(); return guard(ctx, [&] {
+        ctx->e->no_recorder("mhip_splitting_run");
         if (first < 0 || n < 0 || !std::isfinite(dt)) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_splitting_run: first_step and n_steps must be non-negative, dt finite"};
         if (!(kT >= 0) || !(friction >= 0)) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_splitting_run: temperature and friction must be non-negative"};
         if (!mhip::plan_splitting(splitting, dt).ok) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_splitting_run: splitting must be 1 to 16 characters out of A, B and O"};
@@ -3308,6 +3445,7 @@ int32_t mhip_splitting_run(mhip_ctx* ctx, int64_t first, int64_t n, double dt, d
 }
 int32_t mhip_overdamped_run(mhip_ctx* ctx, int64_t first, int64_t n, double dt, double kT, double friction, int32_t cm_every, uint64_t key, uint64_t ctr1) {
     NEED_CTX(); return guard(ctx, [&] {
+        ctx->e->no_recorder("mhip_overdamped_run");
         if (first < 0 || n < 0 || !std::isfinite(dt)) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_overdamped_run: first_step and n_steps must be non-negative, dt finite"};
         if (!(kT >= 0) || !(friction > 0) || !std::isfinite(friction)) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_overdamped_run: temperature must be non-negative, friction positive and finite"};
         ctx->e->overdamped_run(first, n, dt, kT, friction, cm_every, key, ctr1); });
@@ -3344,7 +3482,7 @@ int32_t mhip_set_pme(mhip_ctx* ctx, int32_t order, const int32_t* mesh, double a
 int32_t mhip_general_forces(mhip_ctx* ctx, int32_t acc, void* f, int32_t mk) { NEED_CTX(); return guard(ctx, [&] { if (!f) throw mhip::ApiError{MHIP_ERR_INVALID, "null force buffer"}; ctx->e->general_forces(acc, f, mk); }); }
 int32_t mhip_general_potential_energy(mhip_ctx* ctx, double* pe) { NEED_CTX(); return guard(ctx, [&] { *pe = ctx->e->general_potential_energy(); }); }
 int32_t mhip_vv_halo_end_parts(mhip_ctx* ctx, int64_t step_n, double dt, int64_t first, int64_t n, const void* in, double* cm_parts, int32_t n_parts) {
-    NEED_CTX(); return guard(ctx, [&] { ctx->e->halo_end_parts(step_n, dt, first, n, in, cm_parts, n_parts); });
+    NEED_CTX(); return guard(ctx, [&] { ctx->e->no_recorder("mhip_vv_halo_end_parts"); ctx->e->halo_end_parts(step_n, dt, first, n, in, cm_parts, n_parts); });
 }
 int32_t mhip_remove_cm_parts_dev(mhip_ctx* ctx, const double* parts, int32_t n_parts) { NEED_CTX(); return guard(ctx, [&] { if (!parts) throw mhip::ApiError{MHIP_ERR_INVALID, "null partials"}; ctx->e->remove_cm_parts_dev(parts, n_parts); }); }
 int32_t mhip_set_ghost_margin(mhip_ctx* ctx, double m) { NEED_CTX(); return guard(ctx, [&] { ctx->e->set_ghost_margin(m); }); }
@@ -3354,12 +3492,12 @@ int32_t mhip_plan_state_dev(mhip_ctx* ctx, float* out3) { NEED_CTX(); return gua
 int32_t mhip_plan_decide(mhip_ctx* ctx, int64_t step_n, const float* reduced3, int32_t* action, int32_t* check_in) {
     NEED_CTX(); return guard(ctx, [&] { if (!reduced3 || !action) throw mhip::ApiError{MHIP_ERR_INVALID, "null argument"}; *action = ctx->e->plan_decide(step_n, reduced3, check_in); });
 }
-int32_t mhip_set_halo_plan(mhip_ctx* ctx, const mhip_halo_plan* plan) { NEED_CTX(); return guard(ctx, [&] { ctx->e->set_halo_plan(plan); }); }
-int32_t mhip_vv_halo_start(mhip_ctx* ctx, double dt) { NEED_CTX(); return guard(ctx, [&] { ctx->e->halo_start(dt); }); }
+int32_t mhip_set_halo_plan(mhip_ctx* ctx, const mhip_halo_plan* plan) { NEED_CTX(); return guard(ctx, [&] { if (plan) ctx->e->no_recorder("mhip_set_halo_plan"); ctx->e->set_halo_plan(plan); }); }
+int32_t mhip_vv_halo_start(mhip_ctx* ctx, double dt) { NEED_CTX(); return guard(ctx, [&] { ctx->e->no_recorder("mhip_vv_halo_start"); ctx->e->halo_start(dt); }); }
 int32_t mhip_vv_halo_mid(mhip_ctx* ctx, int64_t step_n, double dt, int32_t flags, double* cm_parts, int32_t n_parts) {
-    NEED_CTX(); return guard(ctx, [&] { ctx->e->halo_mid(step_n, dt, flags, cm_parts, n_parts); });
+    NEED_CTX(); return guard(ctx, [&] { ctx->e->no_recorder("mhip_vv_halo_mid"); ctx->e->halo_mid(step_n, dt, flags, cm_parts, n_parts); });
 }
-int32_t mhip_halo_region(mhip_ctx* ctx, int64_t rows_capacity, int32_t world, int32_t rank, void* ipc_handle_out) { NEED_CTX(); return guard(ctx, [&] { ctx->e->halo_region(rows_capacity, world, rank, ipc_handle_out); }); }
+int32_t mhip_halo_region(mhip_ctx* ctx, int64_t rows_capacity, int32_t world, int32_t rank, void* ipc_handle_out) { NEED_CTX(); return guard(ctx, [&] { if (world > 1) ctx->e->no_recorder("mhip_halo_region with peers"); ctx->e->halo_region(rows_capacity, world, rank, ipc_handle_out); }); }
 int32_t mhip_halo_open_peer(mhip_ctx* ctx, int32_t rank, const void* ipc_handle) { NEED_CTX(); return guard(ctx, [&] { ctx->e->halo_open_peer(rank, ipc_handle); }); }
 int32_t mhip_set_launch_config(mhip_ctx* ctx, int32_t block_atoms, int32_t j_split) { NEED_CTX(); return guard(ctx, [&] { ctx->e->set_launch_config(block_atoms, j_split); }); }
 int32_t mhip_optimize_launch_config(mhip_ctx* ctx, int32_t n_passes, mhip_launch_trial* trials, int32_t max_trials, int32_t* n_trials) {
@@ -3375,11 +3513,12 @@ int32_t mhip_set_halo_routes(mhip_ctx* ctx, const mhip_halo_routes* routes) { NE
 int32_t mhip_domain_run(mhip_ctx* ctx, int64_t first_step, int64_t n_steps, double dt, int32_t remove_cm_every, double* cm_parts_dev, int32_t n_parts,
                         int64_t* steps_done, int32_t* reason, int64_t* counters3) {
     NEED_CTX(); return guard(ctx, [&] {
+        ctx->e->no_recorder("mhip_domain_run");
         if (!steps_done || !reason || !(dt > 0) || n_steps < 0) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_domain_run: null output, dt <= 0 or n_steps < 0"};
         if (remove_cm_every != 0 && (!cm_parts_dev || n_parts < 1 || n_parts > 1024)) throw mhip::ApiError{MHIP_ERR_INVALID, "mhip_domain_run: n_parts must be 1..1024 when the centre-of-mass motion is removed"};
         ctx->e->domain_run(first_step, n_steps, dt, remove_cm_every, cm_parts_dev, n_parts, steps_done, reason, counters3); });
 }
-int32_t mhip_set_domain(mhip_ctx* ctx, const mhip_domain_geometry* g, const int64_t* gids_dev) { NEED_CTX(); return guard(ctx, [&] { ctx->e->set_domain(g, gids_dev); }); }
+int32_t mhip_set_domain(mhip_ctx* ctx, const mhip_domain_geometry* g, const int64_t* gids_dev) { NEED_CTX(); return guard(ctx, [&] { if (g) ctx->e->no_recorder("mhip_set_domain"); ctx->e->set_domain(g, gids_dev); }); }
 int32_t mhip_set_constraints(mhip_ctx* ctx, int64_t n_dist, const int32_t* i, const int32_t* j, const double* dist, int64_t n_angle, const int32_t* ai, const int32_t* aj,
                              const int32_t* ak, const double* d3, double dist_tol, double vel_tol, int32_t max_iters) {
     NEED_CTX(); return guard(ctx, [&] { ctx->e->set_constraints(n_dist, i, j, dist, n_angle, ai, aj, ak, d3, dist_tol, vel_tol, max_iters); });
@@ -3396,10 +3535,20 @@ int32_t mhip_distribute_forces(mhip_ctx* ctx, void* f, int32_t mk) { NEED_CTX();
 int32_t mhip_virtual_site_info(mhip_ctx* ctx, int64_t* out8) { NEED_CTX(); return guard(ctx, [&] { if (!out8) throw mhip::ApiError{MHIP_ERR_INVALID, "null output"}; ctx->e->virtual_site_info(out8); }); }
 int32_t mhip_domain_info(mhip_ctx* ctx, int64_t* out8) { NEED_CTX(); return guard(ctx, [&] { if (!out8) throw mhip::ApiError{MHIP_ERR_INVALID, "null output"}; ctx->e->domain_info(out8); }); }
 int32_t mhip_domain_export(mhip_ctx* ctx, int64_t* gid_dev, void* par4_dev) { NEED_CTX(); return guard(ctx, [&] { ctx->e->domain_export(gid_dev, par4_dev); }); }
-int32_t mhip_vv_halo_begin(mhip_ctx* ctx, double dt, const int32_t* idx, const void* shift, int64_t n, void* out) { NEED_CTX(); return guard(ctx, [&] { ctx->e->halo_begin(dt, idx, shift, n, out); }); }
-int32_t mhip_vv_halo_interior(mhip_ctx* ctx, int64_t step_n, int32_t* launched) { NEED_CTX(); return guard(ctx, [&] { int r = ctx->e->halo_interior(step_n); if (launched) *launched = r; }); }
-int32_t mhip_vv_halo_end(mhip_ctx* ctx, int64_t step_n, double dt, int64_t first, int64_t n, const void* in, double* cm_out4) {
-    NEED_CTX(); return guard(ctx, [&] { ctx->e->halo_end(step_n, dt, first, n, in, cm_out4); });
+int32_t mhip_vv_halo_begin(mhip_ctx* ctx, double dt, const int32_t* idx, const void* shift, int64_t n, void* out) { NEED_CTX(); return guard(ctx, [&] { ctx->e->no_recorder("mhip_vv_halo_begin"); ctx->e->halo_begin(dt, idx, shift, n, out); }); }
+int32_t mhip_vv_halo_interior(mhip_ctx* ctx, int64_t step_n, int32_t* launched) {
+    NEED_CTX(); return guard(ctx, [&] { ctx->e->no_recorder("mhip_vv_halo_interior"); int r = ctx->e->halo_interior(step_n); if (launched) *launched = r; });
 }
+int32_t mhip_vv_halo_end(mhip_ctx* ctx, int64_t step_n, double dt, int64_t first, int64_t n, const void* in, double* cm_out4) {
+    NEED_CTX(); return guard(ctx, [&] { ctx->e->no_recorder("mhip_vv_halo_end"); ctx->e->halo_end(step_n, dt, first, n, in, cm_out4); });
+}
+// the recorder: apply_loggers! (loggers.jl:44-56) and values(logger) (loggers.jl:96-102, 131-283) on the device
+int32_t mhip_set_record(mhip_ctx* ctx, const int32_t* every4, const int64_t* capacity4) { NEED_CTX(); return guard(ctx, [&] { ctx->e->set_record(every4, capacity4); }); }
+int32_t mhip_record_now(mhip_ctx* ctx, int64_t step_n, int32_t channel_mask) { NEED_CTX(); return guard(ctx, [&] { ctx->e->record_now(step_n, channel_mask); }); }
+int32_t mhip_record_info(mhip_ctx* ctx, int64_t* out16) { NEED_CTX(); return guard(ctx, [&] { if (!out16) throw mhip::ApiError{MHIP_ERR_INVALID, "null output"}; ctx->e->record_info(out16); }); }
+int32_t mhip_record_read(mhip_ctx* ctx, int32_t channel, int64_t first, int64_t n, int64_t* steps_out, void* values_out, int32_t mem_kind) {
+    NEED_CTX(); return guard(ctx, [&] { ctx->e->record_read(channel, first, n, steps_out, values_out, mem_kind); });
+}
+int32_t mhip_record_clear(mhip_ctx* ctx) { NEED_CTX(); return guard(ctx, [&] { ctx->e->record_clear(); }); }
 
 }  // extern "C"

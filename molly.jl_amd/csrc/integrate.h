@@ -296,12 +296,19 @@ __global__ void __launch_bounds__(256) k_scale_vel(int64_t n, typename Vec<T>::T
     }
 }
 
+// One atom's (m/2) v·v in double, every operation written out: vy², + vx² fused, + vz² fused, times m/2 — the form k_ke_partials has always been compiled to,
+// pinned so that every kernel that takes the kinetic energy (k_ke_partials, k_record of record.h) gives the same bits whatever surrounds the expression.
+template <class V4> __device__ inline double ke_atom(const V4& v) {
+    const double x = (double)v.x, y = (double)v.y, z = (double)v.z;
+    return __dmul_rn(__dmul_rn((double)v.w, 0.5), __fma_rn(z, z, __fma_rn(x, x, __dmul_rn(y, y))));
+}
+
 // kinetic energy partials: Σ (m/2) v·v  (energy.jl:56-89)
 template <class T>
 __global__ void k_ke_partials(int64_t n, const typename Vec<T>::T4* __restrict__ vel, double* part) {
     int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     double k = 0;
-    if (s < n) { auto v = vel[s]; k = 0.5 * (double)v.w * ((double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z); }
+    if (s < n) { auto v = vel[s]; k = ke_atom(v); }
     __shared__ double sh[4];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) k += __shfl_xor(k, o, 64);
